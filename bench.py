@@ -19,10 +19,17 @@ registers pairs r, r+R, ... (gh-icp_amd/pairqueue.py) and every step ends with O
     python bench.py --gpus 1 --steps 2 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the kernel's own stream), `cpu_baseline` (the
-oracle = PCL-free restatement of the reference path, g++ -O3 -march=native: 1 thread median of 3, and all host cores; rank 0 at
-N=1 only), `parity_check` (EVERY distinct pair of the batch against the oracle), `single_pair_latency_s`, the true per-pair
-`ms_per_iteration`, and the Kuhn-Munkres launch statistics (longest / mean solve per launch, idle solve slots).
+Prints ONE JSON line (rank 0): the headline (`metric`, `value`, `unit`, `ms_per_step`), `roofline` (dominant kernel, HIP-event timed
+on the kernel's own stream inside the timed steps) and the Kuhn-Munkres launch statistics (longest / mean solve per launch, idle
+solve slots).  A plain run does nothing but set up, warm up, time the steps and print.  `--full` adds what takes runs of its own:
+`cpu_baseline` (the oracle = PCL-free restatement of the reference path, g++ -O3 -march=native: 1 thread median of 3, and all host
+cores; rank 0 at N=1 only), `parity_check` (EVERY distinct pair of the batch against the oracle), `single_pair_latency_s`, the true
+per-pair `ms_per_iteration`, and `value_no_hints` (two more timed regions, with and without the queue-order prior).
+
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (DIR/<name>.npy, dump_outputs below).  The scenes of the
+default workload are generated once by `python bench.py --prepare-scenes` (build() runs it) and read back by every later run.
 """
 import argparse
 import importlib
@@ -73,12 +80,75 @@ def make_pair(config_id, pair_id, hits):
     return synth.tls_pair(hits, config_id=base, pair_id=pair_id, variant=variant)
 
 
+PREPARED_SCENES = os.path.join(ROOT, ".bench_scenes")  # written by --prepare-scenes only; a run reads it when --scene-cache is not given
+
+
+def _scene_file(cache, config_id, pair_id, hits):
+    return os.path.join(cache, "scene_c%d_p%d_h%d.npz" % (config_id, pair_id, hits))
+
+
+def _load_scene(f):
+    z = np.load(f)
+    return z["s"], z["t"], z["gt"]
+
+
+def _usable_cpus():
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 8
+
+
+def load_or_generate_scenes(config_id, scene_ids, hits, write_cache, read_caches, nproc_cap):
+    """{scene id: (source, target, gt)}.  Stored scenes are read in this process (threads: no pickling of 24 MB arrays through a
+    pipe); the others are generated by forked workers -- BEFORE HIP is initialised -- and stored when `write_cache` is set."""
+    from concurrent.futures import ThreadPoolExecutor
+    import multiprocessing as mp
+
+    found = {}
+    for sid in scene_ids:
+        for c in read_caches:
+            if c and os.path.exists(_scene_file(c, config_id, sid, hits)):
+                found[sid] = _scene_file(c, config_id, sid, hits)
+                break
+    scene = {}
+    if found:
+        with ThreadPoolExecutor(min(8, len(found))) as tp:
+            scene.update(zip(found, tp.map(_load_scene, found.values())))
+    todo = [sid for sid in scene_ids if sid not in scene]
+    nproc = max(1, min(len(todo), nproc_cap))
+    if nproc > 1:
+        with mp.get_context("fork").Pool(nproc) as pool:
+            gen = pool.map(_gen_worker, [(config_id, sid, hits, write_cache) for sid in todo])
+    else:
+        gen = [_gen_worker((config_id, sid, hits, write_cache)) for sid in todo]
+    scene.update(zip(todo, gen))
+    return scene
+
+
+def prepare_scenes():
+    """The distinct scenes of the default workload (one GPU), generated once into PREPARED_SCENES: 64 x 2 clouds of 1 M points take a
+    numpy ray caster 10 s each, which a plain run would otherwise pay before its first step every time."""
+    import multiprocessing as mp
+
+    CF = CONFIGS[2]
+    todo = [sid for sid in range(CF["distinct"]) if not os.path.exists(_scene_file(PREPARED_SCENES, 2, sid, CF["hits"]))]
+    nproc = max(1, min(len(todo), _usable_cpus(), 16))
+    if todo:
+        with mp.get_context("fork").Pool(nproc) as pool:
+            pool.map(_prepare_worker, [(2, sid, CF["hits"], PREPARED_SCENES) for sid in todo], chunksize=1)
+    print("scenes of the default workload: %d stored in %s (%d generated now)" % (CF["distinct"], PREPARED_SCENES, len(todo)))
+
+
+def _prepare_worker(a):
+    _gen_worker(a)  # stores the scene; nothing is sent back
+
+
 def _gen_worker(a):
     cache = a[3] if len(a) > 3 else None
-    f = os.path.join(cache, "scene_c%d_p%d_h%d.npz" % a[:3]) if cache else None
+    f = _scene_file(cache, *a[:3]) if cache else None
     if f and os.path.exists(f):  # sweeps of several bench runs in one session: the (untimed) generation is paid once
-        z = np.load(f)
-        return z["s"], z["t"], z["gt"]
+        return _load_scene(f)
     p = make_pair(*a[:3])
     if f:
         os.makedirs(cache, exist_ok=True)
@@ -172,6 +242,31 @@ def pair_bytes(n, m, c, k_s, k_t, V, iters, corr_km, cor, n_src=None):
     return 2.0 * per_cloud + s4 + iters * (s5 + s6) + s7
 
 
+DUMP_POINTS = 4096  # rows kept of every transformed cloud (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, records, stats_rows, clouds):
+    """What the last timed step handed to its caller, as float64 / float32 .npy files (two builds are compared file by file):
+      pair_ids, iterations, converged, Rt (n, 4, 4) -- the result record of every pair of the step's job, all ranks, by pair id;
+      pair_stats (n, 7)                             -- rank 0's pairs: pair id, k_s, k_t, m_s, m_t, rmse_after, registered_ok;
+      transformed_pair_ids, transformed_rows, transformed_points (p, DUMP_POINTS, 3) f32 -- the raw source clouds under their final
+        transform (S7) that are still in the output ring after the step: the same seeded sample of rows of each."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = sorted(records)
+    sv = lambda name, a, dt=np.float64: np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dt))  # noqa: E731
+    sv("pair_ids", ids)
+    sv("iterations", [records[i][0] for i in ids])
+    sv("converged", [records[i][1] for i in ids])
+    sv("Rt", np.array([records[i][2] for i in ids], np.float64).reshape(len(ids), 4, 4))
+    sv("pair_stats", np.array(stats_rows, np.float64).reshape(len(stats_rows), 7))
+    if clouds:
+        n_min = min(int(c.shape[0]) for _, c in clouds)
+        rows = np.sort(np.random.default_rng(0x5EED).choice(n_min, size=min(DUMP_POINTS, n_min), replace=False))
+        sv("transformed_pair_ids", [p for p, _ in clouds])
+        sv("transformed_rows", rows)
+        sv("transformed_points", np.stack([c[rows].cpu().numpy() for _, c in clouds]), np.float32)
+
+
 def compact(d, limit=5000):
     """The driver keeps an 8 KB tail of stdout: the ONE JSON line must stay far below that."""
     line = json.dumps(d, separators=(",", ":"))
@@ -200,7 +295,12 @@ def main():
                     "front-end kernels queue behind Kuhn-Munkres workgroups that hold the CUs' LDS); 2: the front ends of step k+1 start when step k is down "
                     "to its slowly converging pairs (ghicp_ctx_loop_progress), so the long tail of a step overlaps the next step's work")
     ap.add_argument("--tail-fraction", type=float, default=0.15, help="--pipeline 2: a group is in its tail when this fraction of its pairs is still iterating")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 disables the CPU (oracle) legs and the parity check")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the CPU (oracle) legs and the parity check "
+                    "(--cpu-baseline, --cpu-check), the single-pair latency and ms_per_iteration, and the two comparison regions of value_no_hints "
+                    "(--no-hints-steps).  Without it a run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--prepare-scenes", action="store_true", help="generate the scenes of the default workload into %s and exit (no GPU needed)" % os.path.basename(PREPARED_SCENES))
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: 0 disables the CPU (oracle) legs and the parity check")
     ap.add_argument("--fe-batch", type=int, default=-1, help="clouds per batched front-end launch sequence (ghicp_clouds_recompute); 0/1 = cloud by cloud; "
                     "-1 = calibrate: time both front ends on a sample before the warm-up and use the faster one")
     ap.add_argument("--fe-batch-size", type=int, default=32, help="clouds per launch sequence when --fe-batch -1 picks the batched front end")
@@ -208,7 +308,8 @@ def main():
     ap.add_argument("--cpu-check", type=int, default=1, help="0: the CPU legs only TIME the restatement (no second run with the contract build, no parity_check): for the 5 M / "
                     "10 M configurations when box time is short -- their parity at full size is asserted by tests/test_gpu_fullsize.py")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the many-core CPU leg (0 = 64, capped by the host's logical CPUs; the distinct scenes are cycled)")
-    ap.add_argument("--scene-cache", default="", help="directory that keeps the generated synthetic scenes between runs (the generation is untimed)")
+    ap.add_argument("--scene-cache", default="", help="directory that keeps the generated synthetic scenes between runs (the generation is untimed); "
+                    "default: nothing is stored, the scenes that --prepare-scenes stored are read")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of the pair queue: nccl (= RCCL over xGMI, one rank per GPU) or "
                     "gloo (host-side records; lets several ranks share ONE GPU: the N > 1 queue logic on real HIP contexts, SURVEY.md 8e)")
     ap.add_argument("--group", type=int, default=0, help="1: build the process group even for ONE rank, so that the manifest broadcast and the all-gather of the "
@@ -216,12 +317,17 @@ def main():
     ap.add_argument("--queue-hints", type=int, default=1, help="1: the persistent pair loop queues the pairs of a batch costliest first, the cost being what the SAME pair "
                     "needed in the previous step (iterations x n^2; ghicp_ctx_set_loop_cost_hints): the 112-iteration pairs start first instead of in the middle "
                     "of a batch.  0: largest graph first (no history).  Results do not depend on the order")
-    ap.add_argument("--no-hints-steps", type=int, default=2, help="steps of each of the two comparison regions run AFTER the timed one (with and without the queue-order "
+    ap.add_argument("--no-hints-steps", type=int, default=2, help="--full: steps of each of the two comparison regions run AFTER the timed one (with and without the queue-order "
                     "prior) that give `value_no_hints`; 0 skips them")
     ap.add_argument("--queue", default="static", choices=["static", "dynamic"], help="pair queue across ranks: static p mod R, or chunks claimed from a shared counter")
     ap.add_argument("--queue-chunks", type=int, default=8, help="--queue dynamic: claims per rank and step (chunk = job / (ranks x this))")
     ap.add_argument("--detail-dir", default=os.path.join(ROOT, "gpurun_out"), help="where the per-scene / per-kernel side file goes")
     args = ap.parse_args()
+    if args.prepare_scenes:
+        prepare_scenes()
+        return
+    if not args.full:  # a plain run: the headline and what its timed steps give for free
+        args.cpu_baseline, args.no_hints_steps = 0, 0
     CF = CONFIGS[args.config]
     hits = args.hits or CF["hits"]
     distinct = max(1, args.distinct or CF["distinct"])
@@ -248,14 +354,16 @@ def main():
     t0 = time.time()
     import multiprocessing as mp
 
-    nproc = max(1, min(len(my_scenes), (os.cpu_count() or 8) // max(1, world), 32))
-    if nproc > 1:
-        with mp.get_context("fork").Pool(nproc) as pool:
-            gen = pool.map(_gen_worker, [(args.config, sid, hits, args.scene_cache) for sid in my_scenes])
-    else:
-        gen = [_gen_worker((args.config, sid, hits, args.scene_cache)) for sid in my_scenes]
-    scene = {sid: g for sid, g in zip(my_scenes, gen)}
+    scene = load_or_generate_scenes(args.config, my_scenes, hits, args.scene_cache, [args.scene_cache or PREPARED_SCENES],
+                                    max(1, min(_usable_cpus() // max(1, world), 32)))
     gen_s = time.time() - t0
+    phases = {"scenes": round(gen_s, 2)}  # seconds a run spends outside its steps, by phase (side file)
+    tp = time.time()
+
+    def phase(name):
+        nonlocal tp
+        phases[name] = round(time.time() - tp, 2)
+        tp = time.time()
 
     import torch
 
@@ -286,9 +394,11 @@ def main():
     synth = importlib.import_module("gh-icp_amd.synth")
     dev = {sid: (torch.from_numpy(s).cuda(), torch.from_numpy(t).cuda()) for sid, (s, t, _) in scene.items()}
     torch.cuda.synchronize()
+    phase("import_torch_and_upload")
     feature = {"BSC": api.FEATURE_BSC, "FPFH": api.FEATURE_FPFH}[CF["feature"]]
     corr = {"KM": api.CORR_KM, "NN": api.CORR_NN, "NNR": api.CORR_NNR}[CF["corr"]]
     cfg = api.pair_config(feature, corr, CF["dof"], CF["iou"], CF["voxel"], CF["r"], CF["R"], synth.bsc_pattern_glibc(), max_iter=200)
+    cfg_fill = api.pair_config(feature, corr, CF["dof"], CF["iou"], CF["voxel"], CF["r"], CF["R"], synth.bsc_pattern_glibc(), max_iter=1)  # run_pipeline(fill=True)
     nb = len(mine)  # pairs this rank registers per step
     nstream = max(1, min(args.fe_streams, max(1, nb)))
     G = max(1, min(args.loop_groups or (1 if CF["corr"] == "KM" else 3), max(1, nb)))
@@ -348,6 +458,7 @@ def main():
             raise errs[0]
         return 2 * len(sample) / dt
 
+    phase("contexts")
     fe_cal = None
     if args.fe_batch < 0:
         fe_cal = {"sample_pairs": min(nb, 64)}
@@ -403,6 +514,7 @@ def main():
     n_src_max = (max((int(dev[sid][0].shape[0]) for sid in dev), default=1) + 3) & ~3  # 16-byte aligned rows: the float4 path of k_transform_batch
     RING = max(1, min(nb, 256, int(24e9 // max(1, 12 * n_src_max * len(loop_ctxs)))))
     s7_ring = [torch.empty((RING, n_src_max, 3), dtype=torch.float32, device="cuda") for _ in loop_ctxs]
+    s7_last = {}  # loop context -> the pairs its ring holds since its latest launch (--dump-outputs)
 
     def final_transform(ci, pair_ids, stats):
         """pair_ids: indices into `manifest` (global pair ids); stats: their ghicp_pair_stats, same order"""
@@ -411,9 +523,12 @@ def main():
             part = pair_ids[c0:c0 + RING]
             clouds = [dev[manifest[p]][0] for p in part]
             c.transform_clouds(clouds, [stats[c0 + j].Rt[:] for j in range(len(part))], [ring[j, :clouds[j].shape[0]] for j in range(len(part))])
+            s7_last[ci] = list(part)
 
-    def run_pipeline(K):
-        """K steps through the pipeline; returns when every pair of every step is registered and its records are gathered."""
+    def run_pipeline(K, k0=0, fill=False):
+        """K steps through the pipeline; returns when every pair of every step is registered and its records are gathered.  The steps count
+        from k0 (which of the NBUF handle sets and LP loop contexts a step uses goes by k0 + k).  fill: the steps only allocate -- complete
+        front ends, loops of ONE iteration on the full batch -- and leave results and queue-order costs as they are."""
         if K <= 0:
             return
         cv = threading.Condition()
@@ -424,14 +539,14 @@ def main():
         err = []
 
         def tail_reached(kk, gg):
-            a, t = loop_ctxs[gg + G * (kk % LP)].loop_progress()
+            a, t = loop_ctxs[gg + G * ((k0 + kk) % LP)].loop_progress()
             return t > 0 and a <= args.tail_fraction * t
 
         def fe_worker(w):
             try:
                 c = fe_ctxs[w]
                 for k in range(K):
-                    buf = pool_h[k % NBUF]
+                    buf = pool_h[(k0 + k) % NBUF]
                     per = max(1, args.fe_batch // 2) if args.fe_batch > 1 else 1   # pairs per front-end launch sequence
                     if args.pipeline == 1:
                         # group-major: the workers finish group 0's clouds first, then group 1's, ... so that a group's loop starts while the
@@ -496,7 +611,7 @@ def main():
             try:
                 g, par = gp % G, gp // G
                 n_g = bounds[g + 1] - bounds[g]
-                for k in range(par, K, LP):
+                for k in range((par - k0) % LP, K, LP):
                     with cv:  # strict schedule: the loops start when every front end of the step is done
                         cv.wait_for(lambda: (ready[k][g] == n_g if args.pipeline == 1 else sum(ready[k]) == nb) or err)
                     if err:
@@ -507,8 +622,8 @@ def main():
                     t = time.perf_counter()
                     if hints_on[0] and pair_cost[g] is not None and len(pair_cost[g]) == n_g and CF["corr"] == "KM":
                         loop_ctxs[gp].set_loop_cost_hints(pair_cost[g])
-                    r = loop_ctxs[gp].register_clouds(cfg, pool_h[k % NBUF][bounds[g]:bounds[g + 1]]) if n_g else []
-                    if n_g:
+                    r = loop_ctxs[gp].register_clouds(cfg_fill if fill else cfg, pool_h[(k0 + k) % NBUF][bounds[g]:bounds[g + 1]]) if n_g else []
+                    if n_g and not fill:
                         # what the same pair cost last time, as a prior for the queue order and the classes' shares of the chip
                         # (iterations x n, calls 7 and 8 of round 5, scheduled worse than iterations x n^2: profiles/r05_call7_log.txt)
                         pair_cost[g] = [float(st.iterations) * float(max(st.k_s, st.k_t)) ** 2 for st in r]
@@ -546,7 +661,8 @@ def main():
         if err:
             raise err[0]
         for g in range(G):
-            last_results[g] = res[K - 1][g]
+            if not fill:
+                last_results[g] = res[K - 1][g]
 
     # ---- dynamic pair queue (--queue dynamic, N > 1): per step the ranks claim chunks of pair ids from a shared counter until the step's
     # job is drained (gh-icp_amd/pairqueue.py:SharedCounter); the front ends of chunk c + 1 overlap the loop of chunk c (two handle sets)
@@ -644,8 +760,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    phase("front_end_calibration")
     run_steps = run_dynamic if dynamic else run_pipeline
-    run_steps(max(args.warmup, 0))
+    # Every cloud handle of the NBUF sets and every loop context is used once before the timed region.  A warm-up shorter than NBUF steps
+    # is followed by the missing steps as allocation-only ones; no warm-up at all is run as NBUF whole steps (the first timed step wants
+    # the queue-order costs of a whole one)
+    warm = max(args.warmup, 0)
+    run_steps(warm if dynamic or warm > 0 else NBUF)
+    if not dynamic and 0 < warm < NBUF:
+        run_pipeline(NBUF - warm, k0=warm, fill=True)
     if not dynamic and any(h is None for buf in pool_h for h in buf):  # allocate every handle of both buffers outside the timed region
         run_pipeline(NBUF)
     for c in ctxs:
@@ -654,6 +777,7 @@ def main():
     host_log["fe"].clear()
     host_log["loop"].clear()
     barrier()
+    phase("warmup_steps")
     t0 = time.perf_counter()
     host_log["t0"] = t0
     run_steps(args.steps)
@@ -681,6 +805,13 @@ def main():
     pls = [c.pair_loop_stats() for c in loop_ctxs]
     for c in ctxs:
         c.kernel_timing(False)
+    phase("timed_steps")
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        last_ctx = [0] if dynamic else [g + G * ((args.steps - 1) % LP) for g in range(G)]
+        kept = [(p, s7_ring[ci][j, :dev[manifest[p]][0].shape[0]]) for ci in last_ctx for j, p in enumerate(s7_last.get(ci, []))][:512]
+        flat_st = [st for r in results for st in r if r]
+        dump_outputs(args.dump_outputs, job_records,
+                     [[mine[i], st.k_s, st.k_t, st.m_s, st.m_t, st.rmse_after, st.registered_ok] for i, st in enumerate(flat_st)], kept)
 
     # ---- what the queue-order prior is worth (round-4 verdict, weak #7): the headline's queue order uses iterations x n^2 of the SAME pair in
     # the previous step, which a first-time caller does not have.  After the timed region: E more steps with the prior, E without ("largest
@@ -751,10 +882,10 @@ def main():
     V = 4 if CF["dof"] > 4 else 2
     shard_b = max(1, nb // G)
 
-    # ---- single pair on an idle GPU: latency and the true per-pair ms/iteration
+    # ---- single pair on an idle GPU: latency and the true per-pair ms/iteration (--full)
     sid0 = manifest[mine[0]]
     lat, lat_loop, lat_it = [], [], 1
-    for _ in range(1 if hits > 2_000_000 else 3):
+    for _ in range((1 if hits > 2_000_000 else 3) if args.full else 0):
         torch.cuda.synchronize()
         tl = time.perf_counter()
         st1, _ = loop_ctxs[0].register_pair(cfg, dev[sid0][0], dev[sid0][1], want_trace=False)
@@ -762,8 +893,8 @@ def main():
         lat.append(time.perf_counter() - tl)
         lat_loop.append(st1.ms_loop)
         lat_it = max(1, st1.iterations)
-    single_latency = float(np.median(lat))
-    ms_iter_single = float(np.median(lat_loop)) / lat_it
+    single_latency = float(np.median(lat)) if lat else None
+    ms_iter_single = float(np.median(lat_loop)) / lat_it if lat else None
 
     # ---- roofline: per kernel / stage (HIP events on the kernel's own stream, summed over the timed region), the dominant kernel,
     # and the whole pair (SURVEY §8d asks for both)
@@ -950,8 +1081,8 @@ def main():
                           "value_gt_ok": round(rate_all * gt_ok_pairs / nb_eff, 4), "value_reference_verdict_ok": round(rate_all * reg_ok_pairs / nb_eff, 4),
                           "max_rot_vs_gt": round(max(e[0] for e in gt.values()), 4) if gt else None,
                           "max_trans_vs_gt_m": round(max(e[1] for e in gt.values()) * CF.get("unit_m", 1.0), 3) if gt else None},
-        "ms_per_iteration": round(ms_iter_single, 4), "ms_per_iteration_in_batch": round(ms_per_step / max(1.0, it_mean), 2),
-        "single_pair_latency_s": round(single_latency, 4),
+        "ms_per_iteration": round(ms_iter_single, 4) if lat else None, "ms_per_iteration_in_batch": round(ms_per_step / max(1.0, it_mean), 2),
+        "single_pair_latency_s": round(single_latency, 4) if lat else None, "full": bool(args.full),
         "batch_ms": {"front_end_thread_s_per_step": round(thread_busy["front_end"] / max(1, args.steps), 2), "front_end_threads": fe_n,
                      "loop_thread_s_per_step": round(thread_busy["loop"] / max(1, args.steps), 2), "loop_groups": G, "pipeline": args.pipeline,
                      "front_end_ms_per_cloud_on_its_stream": round(1e3 * thread_busy["front_end"] / max(1, args.steps) / max(1, 2 * nb), 4)},
@@ -1006,9 +1137,10 @@ def main():
                           "converged": int(st.converged), "registered_ok": int(st.registered_ok), "rmse_after": float(st.rmse_after),
                           "rot_vs_gt": float(gt[sid][0]) if sid in gt else None, "trans_vs_gt_m": float(gt[sid][1]) * CF.get("unit_m", 1.0) if sid in gt else None,
                           "Rt": [float(v) for v in st.Rt[:]]} for sid, st in sorted(by_scene.items())],
-              "per_kernel": per_kernel, "front_end_calibration": fe_cal, "traffic_source": traffic_src, "gen_seconds": round(gen_s, 1),
+              "per_kernel": per_kernel, "front_end_calibration": fe_cal, "traffic_source": traffic_src, "gen_seconds": round(gen_s, 1), "phases_s": phases,
               "roofline_models": "per-stage bytes: bench.py front_end_bytes_per_cloud / algorithmic_bytes; whole pair: pair_bytes (SURVEY 8d, S0-S7)",
               "line": out}
+    phase("after_the_steps")
     try:
         os.makedirs(args.detail_dir, exist_ok=True)
         with open(os.path.join(args.detail_dir, "bench_detail_cfg%d.json" % args.config), "w") as f:

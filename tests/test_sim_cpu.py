@@ -120,3 +120,51 @@ def test_bench_py_two_ranks_on_the_host_simt_interpreter(queue):
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["pairs_per_step"] == 6 and out["value_all_pairs"] > 0 and out["value"] <= out["value_all_pairs"]
     assert len(out["rank_wall_s"]["per_rank"]) == 2 and len(lines[0]) < 6000
     assert ("(%s)" % queue) in out["config"]["parallelism"]  # static p mod R, or chunks claimed from the shared counter (pairqueue.SharedCounter)
+
+
+def test_bench_py_plain_and_full_runs_dump_the_same_outputs(tmp_path):
+    """A plain run is the headline alone; `--full` adds the CPU legs, the parity check, the single-pair latency.  Both are given
+    `--dump-outputs` and must write the same arrays (same arguments -> same inputs -> same results): the result record of every pair of the
+    last timed step, and a seeded sample of every raw source cloud under the 4x4 the step returned for it."""
+    import json
+
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    from hipsim import build
+
+    import bench
+
+    build.build()
+    job = ["--config", "4", "--hits", "20000", "--distinct", "2", "--pairs-per-step", "4", "--steps", "2", "--warmup", "1"]
+    outs = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--cpu-procs", "2"])):
+        d = str(tmp_path / tag)
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "hipsim", "run_bench_sim.py")] + job + extra + ["--dump-outputs", d]
+        r = subprocess.run(cmd, env=dict(os.environ, HIPSIM_THREADS="4"), cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["metric"] == "registered_pairs_per_sec" and line["unit"] == "pairs/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["full"] == (tag == "full")
+        outs[tag] = (line, {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    plain, full = outs["plain"][0], outs["full"][0]
+    # what takes runs of its own is behind --full
+    for key in ("cpu_baseline", "parity_check", "single_pair_latency_s", "ms_per_iteration"):
+        assert plain[key] is None and full[key] is not None, key
+    assert full["parity_check"]["pairs_checked"] == 2 and full["parity_check"]["all_ok"], full["parity_check"]
+    assert full["cpu_baseline"]["value"] > 0 and full["single_pair_latency_s"] > 0 and "speedup_vs_cpu_1thread" in full
+    a, b = outs["plain"][1], outs["full"][1]
+    assert set(a) == set(b) == {"pair_ids", "iterations", "converged", "Rt", "pair_stats", "transformed_pair_ids", "transformed_rows", "transformed_points"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k], equal_nan=True), k
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["Rt"].shape == (4, 4, 4) and a["pair_ids"].tolist() == [0, 1, 2, 3] and a["iterations"].min() >= 1
+    assert a["transformed_points"].shape == (4, min(bench.DUMP_POINTS, 20000), 3) and a["transformed_pair_ids"].tolist() == [0, 1, 2, 3]
+    rows = a["transformed_rows"].astype(np.int64)
+    for j, pid in enumerate(a["transformed_pair_ids"].astype(np.int64)):
+        src = bench.make_pair(4, int(pid) % 2, 20000).source[rows].astype(np.float64)  # pair p of the job is scene p mod --distinct
+        Rt = a["Rt"][int(pid)]
+        want = src @ Rt[:3, :3].T + Rt[:3, 3]
+        if np.isfinite(Rt).all():
+            assert np.abs(a["transformed_points"][j] - want).max() < 1e-5 * max(1.0, np.abs(want).max()), pid  # f32 arithmetic: a few 2^-24 of the coordinates
