@@ -53,7 +53,7 @@ EXPORTS = [
     "ghicp_rigid_svd", "ghicp_rigid_svd_host", "ghicp_register", "ghicp_loop_create", "ghicp_iterate", "ghicp_loop_result", "ghicp_loop_destroy", "ghicp_transform_cloud", "ghicp_transform_clouds", "ghicp_register_pair",
     "ghicp_register_pairs",
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
-    "ghicp_transform_cloud_f32",
+    "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
     "ghicp_register_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
@@ -121,6 +121,23 @@ def icp_params(max_iter=50, reciprocal=False, trimmed=False, metric=ICP_POINT_TO
     load().ghicp_icp_params_default(C.byref(p))
     p.max_iter, p.use_reciprocal, p.use_trimmed, p.metric = max_iter, int(reciprocal), int(trimmed), metric
     p.thre_dis, p.min_overlap, p.covariance_k = thre_dis, min_overlap, covariance_k
+    return p
+
+
+class GicpParams(C.Structure):
+    """ghicp_gicp_params: the arguments of CRegistration::gicp_reg (common_reg.cpp:216-265) + the GICP constants (ghicp_c.h)."""
+    _fields_ = [("max_iter", C.c_int32), ("use_reciprocal", C.c_int32), ("use_trimmed", C.c_int32), ("covariance_k", C.c_int32),
+                ("thre_dis", C.c_float), ("min_overlap", C.c_float), ("max_inner_iter", C.c_int32), ("pad_", C.c_int32),
+                ("max_correspondence_distance", C.c_double), ("gicp_epsilon", C.c_double), ("transformation_epsilon", C.c_double),
+                ("rotation_epsilon", C.c_double)]
+
+
+def gicp_params(max_iter=50, reciprocal=False, trimmed=False, thre_dis=0.5, min_overlap=0.1, covariance_k=20,
+                max_correspondence_distance=1e6, max_inner_iter=20) -> GicpParams:
+    p = GicpParams()
+    load().ghicp_gicp_params_default(C.byref(p))
+    p.max_iter, p.use_reciprocal, p.use_trimmed, p.covariance_k = max_iter, int(reciprocal), int(trimmed), covariance_k
+    p.thre_dis, p.min_overlap, p.max_correspondence_distance, p.max_inner_iter = thre_dis, min_overlap, max_correspondence_distance, max_inner_iter
     return p
 
 
@@ -540,6 +557,27 @@ class Context:
         d = {k: getattr(st, k) for k, _ in IcpStats._fields_ if k != "pad_"}
         d.update(T=T.reshape(4, 4), transformed=out)
         return d
+
+    def gicp(self, xyzS, xyzT, params: GicpParams, want_transformed=True):
+        """gicp_reg.  Returns the dict of icp(): done, T (4,4) f32, transformed tensor, + ghicp_icp_stats fields."""
+        t = self.torch
+        xS, xT = self._xyz(xyzS), self._xyz(xyzT)
+        T = np.zeros(16, np.float32)
+        out = t.empty((xS.shape[0], 3), dtype=t.float32, device=self.dev) if want_transformed else None
+        st = IcpStats()
+        self._check(self.lib.ghicp_gicp(self.h, _ptr(xS), C.c_int64(xS.shape[0]), xS.shape[1], _ptr(xT), C.c_int64(xT.shape[0]), xT.shape[1],
+                                        C.byref(params), T.ctypes.data_as(C.POINTER(C.c_float)), _ptr(out), C.byref(st)))
+        d = {k: getattr(st, k) for k, _ in IcpStats._fields_ if k != "pad_"}
+        d.update(T=T.reshape(4, 4), transformed=out)
+        return d
+
+    def gicp_covariances(self, xyz, k, eps=1e-3):
+        """ghicp_gicp_covariances: (n, 6) f64 tensor (c00, c01, c02, c11, c12, c22)."""
+        t = self.torch
+        x = self._xyz(xyz)
+        out = t.empty((x.shape[0], 6), dtype=t.float64, device=self.dev)
+        self._check(self.lib.ghicp_gicp_covariances(self.h, _ptr(x), C.c_int64(x.shape[0]), x.shape[1], int(k), C.c_double(eps), _ptr(out)))
+        return out
 
     def register_pair(self, cfg: PairConfig, xyzS, xyzT, want_trace=True):
         xS, xT = self._xyz(xyzS), self._xyz(xyzT)

@@ -80,6 +80,8 @@ enum BufSlot {
   B_ICP_SC_KEYS, B_ICP_SC_KEYS2, B_ICP_SC_VALS, B_ICP_SC_VALS2, B_ICP_SC_START, B_ICP_SC_PTS,
   B_ICP_CUR, B_ICP_Q, B_ICP_NN, B_ICP_ND, B_ICP_NN2, B_ICP_ND2, B_ICP_KEYS, B_ICP_KEYS2, B_ICP_SORTTMP, B_ICP_PART, B_ICP_STATE,
   B_ICP_PEND, B_ICP_TNRM, B_ICP_OUT,
+  // generalized ICP (icp.hip): covariances of both clouds, per-correspondence Mahalanobis matrices, the packed source
+  B_GICP_COVS, B_GICP_COVT, B_GICP_MAHAL, B_GICP_SRC4,
   B_NUM
 };
 
@@ -383,4 +385,5 @@ int gh_fd_bsc_batch_dev(ghicp_ctx* ctx, int nb, const gh_fd_bsc_job* jobs);  // 
 int gh_register_dev(ghicp_ctx* ctx, const ghicp_params* p, const double* kpS, int ks, const double* kpT, int kt, const void* FD,
                     double* Rt16, ghicp_iter* trace, int32_t* n_iter, int32_t* matchlist);
 int gh_knn_normals_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, float* normals);
+int gh_gicp_cov_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, double eps, double* cov6);
 int gh_km_solve_dev(ghicp_ctx* ctx, const double* w, int n, double eps, int32_t* match, const int* done_flag);

@@ -131,6 +131,31 @@ __global__ __launch_bounds__(128) void k_knn_batch(const float4* __restrict__ pt
   knn_point(G, 1.0f / G.d.inv, kk, P, nn, nd, nk);
 }
 
+// The kk neighbours' f64 mean and 1/kk scatter (two passes, neighbour order = (d2, index)), rounded by N2, then Jacobi (N3): S ends as
+// the eigenvalues on its diagonal (S[0], S[3], S[5]), V holds the eigenvectors in its columns, im is the smallest (first on ties).
+__device__ inline int knn_scatter_eigen(const float* __restrict__ xyz, int stride, long long i, int kk, const int* __restrict__ nn, double S[6], double V[9]) {
+  double c[3] = {0, 0, 0};
+  for (int t = 0; t < kk; t++) {
+    const long long j = nn[i * KNN + t];
+    c[0] += (double)xyz[j * stride]; c[1] += (double)xyz[j * stride + 1]; c[2] += (double)xyz[j * stride + 2];
+  }
+  c[0] /= kk; c[1] /= kk; c[2] /= kk;
+  for (int t = 0; t < 6; t++) S[t] = 0;
+  for (int t = 0; t < kk; t++) {
+    const long long j = nn[i * KNN + t];
+    const double dx = xyz[j * stride] - c[0], dy = xyz[j * stride + 1] - c[1], dz = xyz[j * stride + 2] - c[2];
+    S[0] += dx * dx; S[1] += dx * dy; S[2] += dx * dz; S[3] += dy * dy; S[4] += dy * dz; S[5] += dz * dz;
+  }
+  for (int t = 0; t < 6; t++) S[t] /= kk;
+  gh_quant_grid(S, 6);
+  gh_jacobi3(S[0], S[1], S[2], S[3], S[4], S[5], V);
+  int im = 0;
+  double ev = S[0];
+  if (S[3] < ev) { im = 1; ev = S[3]; }
+  if (S[5] < ev) { im = 2; }
+  return im;
+}
+
 __global__ __launch_bounds__(256) void k_normals(const float* __restrict__ xyz, int stride, long long m, const int* __restrict__ nn,
                                                  const int* __restrict__ nk, float* __restrict__ normals, int check_normals) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
@@ -140,31 +165,30 @@ __global__ __launch_bounds__(256) void k_normals(const float* __restrict__ xyz, 
     normals[i * 3] = 0.577f; normals[i * 3 + 1] = 0.577f; normals[i * 3 + 2] = 0.577f;
     return;
   }
-  double c[3] = {0, 0, 0};
-  for (int t = 0; t < kk; t++) {
-    const long long j = nn[i * KNN + t];
-    c[0] += (double)xyz[j * stride]; c[1] += (double)xyz[j * stride + 1]; c[2] += (double)xyz[j * stride + 2];
-  }
-  c[0] /= kk; c[1] /= kk; c[2] /= kk;
-  double S[6] = {0, 0, 0, 0, 0, 0};
-  for (int t = 0; t < kk; t++) {
-    const long long j = nn[i * KNN + t];
-    const double dx = xyz[j * stride] - c[0], dy = xyz[j * stride + 1] - c[1], dz = xyz[j * stride + 2] - c[2];
-    S[0] += dx * dx; S[1] += dx * dy; S[2] += dx * dz; S[3] += dy * dy; S[4] += dy * dz; S[5] += dz * dz;
-  }
-  for (int t = 0; t < 6; t++) S[t] /= kk;
-  gh_quant_grid(S, 6);
-  double V[9];
-  gh_jacobi3(S[0], S[1], S[2], S[3], S[4], S[5], V);
-  int im = 0;
-  double ev = S[0];
-  if (S[3] < ev) { im = 1; ev = S[3]; }
-  if (S[5] < ev) { im = 2; }
+  double S[6], V[9];
+  const int im = knn_scatter_eigen(xyz, stride, i, kk, nn, S, V);
   float nx = (float)V[0 * 3 + im], ny = (float)V[1 * 3 + im], nz = (float)V[2 * 3 + im];
   const float vx = 0.f - xyz[i * stride], vy = 0.f - xyz[i * stride + 1], vz = 0.f - xyz[i * stride + 2];
   const float cs = (vx * nx + vy * ny) + vz * nz;  // flipNormalTowardsViewpoint, viewpoint (0,0,0)
   if (cs < 0) { nx = -nx; ny = -ny; nz = -nz; }
   normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
+}
+
+// GICP's regularised covariance (ghicp_c.h: ghicp_gicp): the scatter's eigenvectors with the spectrum replaced by (1, 1, eps),
+// C_rc = (u_r u_c + v_r v_c) + eps * (w_r w_c) with w the smallest eigenvector.  Out: c00, c01, c02, c11, c12, c22.
+__global__ __launch_bounds__(256) void k_gicp_cov(const float* __restrict__ xyz, int stride, long long m, const int* __restrict__ nn,
+                                                  const int* __restrict__ nk, double eps, double* __restrict__ cov6) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= m) return;
+  double S[6], V[9];
+  const int im = knn_scatter_eigen(xyz, stride, i, nk[i], nn, S, V);
+  const int a = im == 0 ? 1 : 0, b = im == 2 ? 1 : 2;
+  const int rr[6] = {0, 0, 0, 1, 1, 2}, cc[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+  for (int e = 0; e < 6; e++) {
+    const int r = rr[e], c = cc[e];
+    cov6[i * 6 + e] = (V[r * 3 + a] * V[c * 3 + a] + V[r * 3 + b] * V[c * 3 + b]) + eps * (V[r * 3 + im] * V[c * 3 + im]);
+  }
 }
 
 __device__ inline float dot3f(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -315,9 +339,8 @@ int gh_fpfh_batch_dev(ghicp_ctx* ctx, const float4* dsg, int M, const float4* pt
 
 // PrincipleComponentAnalysis::CalculateNormalVector_KNN (include/pca.h:92-109): pcl::NormalEstimation with setKSearch(k)
 // followed by CheckNormals.  Shares the exact-kNN and covariance kernels with the FPFH path; k <= 20.
-int gh_knn_normals_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, float* normals) {
-  if (m <= 0) return GHICP_OK;
-  if (k < 1 || k > KNN) return ctx->fail(GHICP_ERR_ARG, "knn normals: k must be in [1, %d]", KNN);
+// exact k-NN lists of every point of one cloud (rows KNN wide, sorted by (d2, index)) in B_FE_SORTK / B_FE_COUNT
+static int knn_lists(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, int** nn_out, int** nk_out) {
   hipStream_t s = ctx->stream;
   float mm[6];
   GH_TRY(gh_bbox_dev(ctx, xyz, m, stride, mm));
@@ -334,7 +357,28 @@ int gh_knn_normals_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride
   GH_TRY(ctx->reserve(B_FE_COUNT, (size_t)m + 1, &nk));
   GridArgs A = {G.d, G.pts, G.start};
   hipLaunchKernelGGL(k_knn, dim3(cdiv(m, 128)), dim3(128), 0, s, A, 1.0f / G.d.inv, k, nn, nd, nk);
-  hipLaunchKernelGGL(k_normals, dim3(cdiv(m, 256)), dim3(256), 0, s, xyz, stride, m, nn, nk, normals, 1);
+  *nn_out = nn;
+  *nk_out = nk;
+  return GHICP_OK;
+}
+
+int gh_knn_normals_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, float* normals) {
+  if (m <= 0) return GHICP_OK;
+  if (k < 1 || k > KNN) return ctx->fail(GHICP_ERR_ARG, "knn normals: k must be in [1, %d]", KNN);
+  int *nn, *nk;
+  GH_TRY(knn_lists(ctx, xyz, m, stride, k, &nn, &nk));
+  hipLaunchKernelGGL(k_normals, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, xyz, stride, m, nn, nk, normals, 1);
+  GH_HIP(hipGetLastError());
+  return GHICP_OK;
+}
+
+// the covariances of GeneralizedIterativeClosestPoint (computeCovariances with k_correspondences_ = k) over the same k-NN lists
+int gh_gicp_cov_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, int k, double eps, double* cov6) {
+  if (m <= 0) return GHICP_OK;
+  if (k < 1 || k > KNN) return ctx->fail(GHICP_ERR_ARG, "gicp covariances: k must be in [1, %d]", KNN);
+  int *nn, *nk;
+  GH_TRY(knn_lists(ctx, xyz, m, stride, k, &nn, &nk));
+  hipLaunchKernelGGL(k_gicp_cov, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, xyz, stride, m, nn, nk, eps, cov6);
   GH_HIP(hipGetLastError());
   return GHICP_OK;
 }

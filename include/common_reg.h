@@ -3,15 +3,19 @@
 // the GPU through the C ABI (ghicp_icp, ghicp_cal_overlap, ghicp_transform_cloud_f32, ghicp_inv_transform).
 //   icp_reg        common_reg.cpp:45-107    point-to-point, closed-form SVD per iteration
 //   ptplicp_reg    common_reg.cpp:122-199   point-to-plane LLS; normals by k-NN PCA (covariance_K <= 20)
+//   gicp_reg       common_reg.cpp:216-284   generalized (plane-to-plane) ICP: k-NN covariances, Mahalanobis matrices,
+//                  Gauss-Newton inner solver (ghicp_c.h: ghicp_gicp).  use_reciprocal_correspondence has no
+//                  effect and use_trimmed_rejector is only the overlap gate, as in the reference (PCL's GICP never consults
+//                  the rejector, common_reg.cpp:213-215)
 //   calOverlap     common_reg.cpp:294-317
 //   transformcloud common_reg.cpp:325-349
 //   invTransform   common_reg.cpp:357-370   (R^T with the negated translation -- "Not Mathimatically" an inverse)
 //   CSTRAN_4DOF / CSTRAN_7DOF / LLS_4DOF / SVD_6DOF   common_reg.cpp:425-888: closed-form fits from a handful of control
 //                  points; host arithmetic (normal equations in f64; SVD_6DOF = the float Umeyama of the path through
 //                  ghicp_rigid_svd_host), no kernel launch
-// Differences a caller can observe: ptplicp_reg and SVD_6DOF return true (the reference falls off the end of a bool
-// function); (A^T A)^-1 A^T b is solved by elimination with partial pivoting instead of an explicit inverse (agrees to
-// rounding); gicp_reg / Coarsereg_FPFHSAC are not part of the hot path and are not provided.
+// Differences a caller can observe: ptplicp_reg, gicp_reg and SVD_6DOF return true (the reference falls off the end of a
+// bool function); (A^T A)^-1 A^T b is solved by elimination with partial pivoting instead of an explicit inverse (agrees to
+// rounding); gicp_reg's inner minimisation is Gauss-Newton, not PCL's BFGS; Coarsereg_FPFHSAC is not provided.
 #ifndef GHICP_DROPIN_COMMON_REG_H_
 #define GHICP_DROPIN_COMMON_REG_H_
 #include <cmath>
@@ -36,6 +40,38 @@ template <typename PointT> class CRegistration {
                    bool use_reciprocal_correspondence, bool use_trimmed_rejector, float thre_dis, int covariance_K, float min_overlap_for_reg) {
     return run(GHICP_ICP_POINT_TO_PLANE, "Point-to-Plane", SourceCloud, TargetCloud, TransformedSource, transformationS2T, max_iter,
                use_reciprocal_correspondence, use_trimmed_rejector, thre_dis, covariance_K, min_overlap_for_reg);
+  }
+
+  bool gicp_reg(const typename pcl::PointCloud<PointT>::Ptr& SourceCloud, const typename pcl::PointCloud<PointT>::Ptr& TargetCloud,
+                typename pcl::PointCloud<PointT>::Ptr& TransformedSource, Eigen::Matrix4f& transformationS2T, int max_iter,
+                bool use_reciprocal_correspondence, bool use_trimmed_rejector, float thre_dis, int covariance_K, float min_overlap_for_reg) {
+    const clock_t t0 = clock();
+    ghicp_gicp_params p;
+    ghicp_gicp_params_default(&p);  // max correspondence distance 1e6, epsilons 1e-8 / 1e-6 (common_reg.cpp:253-265)
+    p.max_iter = max_iter;
+    p.use_reciprocal = use_reciprocal_correspondence ? 1 : 0;
+    p.use_trimmed = use_trimmed_rejector ? 1 : 0;
+    p.thre_dis = thre_dis;
+    p.min_overlap = min_overlap_for_reg;
+    p.covariance_k = covariance_K;
+    const size_t n = SourceCloud->points.size();
+    std::vector<float> xyz(n * 3 + 3);
+    float T16[16];
+    detail::check(ghicp_gicp(detail::ctx(), detail::xyz(*SourceCloud), (int64_t)n, detail::stride<PointT>(), detail::xyz(*TargetCloud),
+                             (int64_t)TargetCloud->points.size(), detail::stride<PointT>(), &p, T16, xyz.data(), &last_stats));
+    if (!last_stats.done) {
+      std::cout << "The overlap ratio is too small. This registration would not be done." << std::endl;  // common_reg.cpp:243-245
+      return false;
+    }
+    TransformedSource->points.clear();  // gicp.align(*TransformedSource) overwrites the output cloud
+    append_xyz(xyz, n, *TransformedSource);
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) transformationS2T(r, c) = T16[r * 4 + c];
+    std::cout << "GICP done in " << float(clock() - t0) / CLOCKS_PER_SEC << " s" << std::endl;  // common_reg.cpp:281-283
+    for (int r = 0; r < 4; r++) std::cout << T16[r * 4] << " " << T16[r * 4 + 1] << " " << T16[r * 4 + 2] << " " << T16[r * 4 + 3] << std::endl;
+    std::cout << "The fitness score of this registration is " << last_stats.fitness << std::endl;
+    std::cout << "-----------------------------------------------------------------------------" << std::endl;
+    return true;
   }
 
   float calOverlap(const typename pcl::PointCloud<PointT>::Ptr& Cloud1, const typename pcl::PointCloud<PointT>::Ptr& Cloud2, float thre_dis) {
@@ -179,7 +215,7 @@ template <typename PointT> class CRegistration {
 
   double last_check_rmse = -1.0;  // RMSE over the check points of the last control-point solver call
 
-  // statistics of the last icp_reg / ptplicp_reg call (the reference only logs them)
+  // statistics of the last icp_reg / ptplicp_reg / gicp_reg call (the reference only logs them)
   ghicp_icp_stats last_stats = {};
 
  private:

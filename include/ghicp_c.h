@@ -328,6 +328,48 @@ void ghicp_inv_transform(const float* T16, float* inv16);
 /* CRegistration::transformcloud (common_reg.cpp:325-349): float 4x4 * (x, y, z, 1). */
 int ghicp_transform_cloud_f32(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, const float* T16 /*[host]*/, float* out /*n x 3*/);
 
+/* CRegistration::gicp_reg (common_reg.cpp:216-284): pcl::GeneralizedIterativeClosestPoint configured by the reference.  PCL's GICP
+ * as recalled (PCL 1.7 / 1.8; not checked against its sources -- this comment and DESIGN.md §4a are the one place to correct it):
+ *   covariances  every point's k nearest neighbours in its own cloud (query included), mean + 1/k scatter, eigenvectors U,
+ *                C = U diag(1, 1, gicp_epsilon) U^T (the smallest eigenvalue replaced by gicp_epsilon), f64
+ *   outer loop   source points under transformation_ (float), 1-NN in the target, kept if d^2 < max_correspondence_distance^2;
+ *                per correspondence M_i = (R C_S,i R^T + C_T,j)^-1 in f64 (R of transformation_)
+ *   inner        minimise (1/c) sum r_i^T M_i r_i over x = (tx, ty, tz, roll, pitch, yaw), R(x) = Rz(yaw) Ry(pitch) Rx(roll),
+ *                from the parameters of transformation_.  PCL uses BFGS; here the solver is the contract's own:
+ *                Gauss-Newton with the analytic Jacobian, at most max_inner_iter steps, stop once max |dx| < 1e-10.
+ *                Fewer than 4 correspondences: PCL throws and the loop stops unconverged (reason GHICP_ICP_NO_CORRESPONDENCES).
+ *   convergence  delta = max over the 4x4 of |prev - cur|, the 3x3 block scaled by 1/rotation_epsilon, the rest by
+ *                1/transformation_epsilon; converged when iterations >= max_iter (GHICP_ICP_ITERATIONS) or delta < 1
+ *                (GHICP_ICP_TRANSFORM)
+ *   output       final = transformation_, transformed = final * S, fitness = getFitnessScore()
+ * GICP's computeTransformation does its own 1-NN search: the reference's reciprocal flag has no effect and its trimmed rejector is
+ * never consulted (common_reg.cpp:213-215).  use_trimmed therefore acts only as the overlap gate (refusal below min_overlap). */
+typedef struct ghicp_gicp_params {
+  int32_t max_iter;        /* gicp_reg argument */
+  int32_t use_reciprocal;  /* accepted, no effect (see above) */
+  int32_t use_trimmed;     /* overlap gate only: calOverlap(S, T, thre_dis) < min_overlap refuses */
+  int32_t covariance_k;    /* setCorrespondenceRandomness: k of the covariances of both clouds, 1..20 */
+  float thre_dis;
+  float min_overlap;
+  int32_t max_inner_iter;  /* Gauss-Newton steps per outer iteration, 1..100 (20) */
+  int32_t pad_;
+  double max_correspondence_distance; /* 1e6 (common_reg.cpp:253) */
+  double gicp_epsilon;                /* 1e-3 */
+  double transformation_epsilon;      /* 1e-8 (common_reg.cpp:263) */
+  double rotation_epsilon;            /* 1e-6 (common_reg.cpp:265) */
+} ghicp_gicp_params;
+
+/* GHICP_ERR_ARG when p is NULL. */
+int ghicp_gicp_params_default(ghicp_gicp_params* p);
+
+/* CRegistration::gicp_reg.  Same conventions as ghicp_icp: T16 row-major float 4x4 [host], transformed ns x 3 or NULL; stats->mse is the
+ * mean squared 1-NN distance of the last iteration's correspondences. */
+int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+               const ghicp_gicp_params* params, float* T16 /*[host]*/, float* transformed, ghicp_icp_stats* stats /*[host]*/);
+
+/* The regularised covariances of one cloud as ghicp_gicp computes them: n x 6 f64 (c00, c01, c02, c11, c12, c22). k in 1..20. */
+int ghicp_gicp_covariances(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, int k, double eps, double* cov6);
+
 /* ------------------------------------------------------------------------------------------------
  * Per-cloud front-end cache (multi-view / all-pairs registration): down-sampling, keypoints and
  * descriptors of one cloud (test/ghicp_main.cpp:86-127) computed once and kept in HBM; a pair then costs
