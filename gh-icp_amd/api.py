@@ -48,7 +48,7 @@ class PairStats(C.Structure):
 EXPORTS = [
     "ghicp_ctx_create", "ghicp_ctx_destroy", "ghicp_ctx_set_stream", "ghicp_ctx_set_host_pointers", "ghicp_ctx_stage_stats", "ghicp_ctx_stage_clear", "ghicp_ctx_set_cu_mask",
     "ghicp_ctx_synchronize", "ghicp_ctx_kernel_timing", "ghicp_ctx_kernel_time", "ghicp_ctx_km_launch_stats", "ghicp_ctx_pair_loop_stats", "ghicp_ctx_loop_timeline", "ghicp_ctx_set_loop_cost_hints", "ghicp_ctx_loop_progress", "ghicp_ctx_loop_progress_reset", "ghicp_ctx_loop_hazards", "ghicp_last_error", "ghicp_version", "ghicp_params_default",
-    "ghicp_voxel_filter", "ghicp_sort_pairs", "ghicp_gather_points", "ghicp_bbx_magnitude", "ghicp_cloud_bounds", "ghicp_pca_curvature", "ghicp_prune",
+    "ghicp_voxel_filter", "ghicp_sort_pairs", "ghicp_scan_inclusive_u32", "ghicp_select_flagged", "ghicp_unique_sorted_u32", "ghicp_gather_points", "ghicp_bbx_magnitude", "ghicp_cloud_bounds", "ghicp_pca_curvature", "ghicp_prune",
     "ghicp_nms", "ghicp_keypoints", "ghicp_keypoints_adaptive", "ghicp_bsc_encode", "ghicp_fpfh", "ghicp_fpfh_keypoints", "ghicp_fd_bsc", "ghicp_fd_fpfh", "ghicp_km_solve",
     "ghicp_rigid_svd", "ghicp_rigid_svd_host", "ghicp_register", "ghicp_loop_create", "ghicp_iterate", "ghicp_loop_result", "ghicp_loop_destroy", "ghicp_transform_cloud", "ghicp_transform_clouds", "ghicp_register_pair",
     "ghicp_register_pairs",
@@ -387,21 +387,58 @@ class Context:
         self._check(self.lib.ghicp_voxel_filter(self.h, _ptr(x), C.c_int64(n), x.shape[1], C.c_float(voxel), _ptr(keep), C.byref(m)))
         return keep[: m.value]
 
-    def sort_pairs(self, keys, vals=None, bit_begin=0, bit_end=None):
-        """stable ascending sort on the key bits [bit_begin, bit_end) (prims.hip); keys: int32 / int64 tensor or array holding u32 / u64 bit patterns"""
+    def sort_pairs(self, keys, vals=None, bit_begin=0, bit_end=None, keys_out=None, vals_out=None):
+        """stable ascending sort on the key bits [bit_begin, bit_end) (prims.hip); keys: int32 / int64 tensor or array holding u32 / u64 bit patterns.
+        keys_out / vals_out: device tensors to sort into (default: fresh ones); they go to the library as they are."""
         t = self.torch
         k = self._dev(keys, None)
         assert k.dtype in (t.int32, t.int64) and k.dim() == 1
         kb = 4 if k.dtype == t.int32 else 8
         n = k.shape[0]
-        ko = t.empty_like(k)
+        ko = t.empty_like(k) if keys_out is None else keys_out
+        assert ko.dtype == k.dtype and ko.shape == k.shape and ko.is_contiguous()
         v = vo = None
         if vals is not None:
             v = self._dev(vals, t.int32)
-            vo = t.empty_like(v)
+            vo = t.empty_like(v) if vals_out is None else vals_out
+            assert vo.dtype == t.int32 and vo.shape == v.shape and vo.is_contiguous()
         self._check(self.lib.ghicp_sort_pairs(self.h, kb, _ptr(k), _ptr(ko), _ptr(v) if v is not None else None, _ptr(vo) if vo is not None else None,
                                               C.c_int64(n), int(bit_begin), int(8 * kb if bit_end is None else bit_end)))
         return (ko, vo) if vals is not None else ko
+
+    def scan_inclusive(self, data):
+        """inclusive prefix sum modulo 2^32 IN PLACE (prims.hip): data is a 1-d int32 device tensor (u32 bit patterns), e.g. a slice of a larger
+        one -- its pointer goes to the library as it is"""
+        t = self.torch
+        assert data.dtype == t.int32 and data.dim() == 1 and data.is_contiguous() and data.device == self.dev
+        self._check(self.lib.ghicp_scan_inclusive_u32(self.h, _ptr(data), C.c_int64(data.shape[0])))
+        return data
+
+    def select_flagged(self, flags, vals=None, out=None):
+        """the positions i with flags[i] != 0 (uint8), ascending -- or vals[i] (int32 holding u32) of those positions; returns out[:count].
+        out: an int32 device tensor of len(flags) items to write into (default: a fresh one)."""
+        t = self.torch
+        f = self._dev(flags, t.uint8)
+        n = f.shape[0]
+        v = None if vals is None else self._dev(vals, t.int32)
+        assert f.dim() == 1 and (v is None or v.shape == f.shape)
+        o = t.empty(n, dtype=t.int32, device=self.dev) if out is None else out
+        assert o.dtype == t.int32 and o.shape == (n,) and o.is_contiguous()
+        m = C.c_int64(-1)
+        self._check(self.lib.ghicp_select_flagged(self.h, _ptr(f), _ptr(v), C.c_int64(n), _ptr(o), C.byref(m)))
+        return o[: m.value]
+
+    def unique_sorted(self, keys, out=None):
+        """the distinct values of an ascending int32 (u32 bit patterns) array, ascending; returns out[:count]"""
+        t = self.torch
+        k = self._dev(keys, t.int32)
+        n = k.shape[0]
+        assert k.dim() == 1
+        o = t.empty(n, dtype=t.int32, device=self.dev) if out is None else out
+        assert o.dtype == t.int32 and o.shape == (n,) and o.is_contiguous()
+        m = C.c_int64(-1)
+        self._check(self.lib.ghicp_unique_sorted_u32(self.h, _ptr(k), C.c_int64(n), _ptr(o), C.byref(m)))
+        return o[: m.value]
 
     def bbx_magnitude(self, xyz):
         x = self._xyz(xyz)

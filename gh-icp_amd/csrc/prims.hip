@@ -86,7 +86,10 @@ __global__ __launch_bounds__(PT) void k_scan_apply(unsigned* __restrict__ data, 
   const long long t0 = (long long)blockIdx.x * TILE + (long long)threadIdx.x * PI;
   unsigned v[PI];
   unsigned acc = 0;
-  const bool whole = t0 + PI <= n;  // 64 bytes per thread, 16-byte aligned (tiles and thread offsets are multiples of 16 items)
+  // 64 bytes per thread as four 16-byte accesses -- only when the thread's range lies inside n AND starts on a 16-byte boundary: t0 is a multiple
+  // of 16 items, so that is a property of `data` alone (uniform over the launch).  A base that is merely 4-byte aligned (batch.hip scans
+  // `table + 1`) takes the item-wise path, like the thread that straddles n.
+  const bool whole = t0 + PI <= n && (reinterpret_cast<uintptr_t>(data) & 15u) == 0;
   if (whole) {
 #pragma unroll
     for (int q = 0; q < PI / 4; q++) {
@@ -506,12 +509,86 @@ int gh_radix_sort_u64(ghicp_ctx* ctx, const unsigned long long* keys_in, unsigne
   return radix_sort_impl<unsigned long long>(ctx, keys_in, keys_out, vals_in, vals_out, n, bit_begin, bit_end);
 }
 
+namespace {
+// [a, a + na) and [b, b + nb) share a byte (null ranges share nothing)
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return a != nullptr && b != nullptr && na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
+}
+// the grand total a select / unique left in device memory -> *count [host]; synchronises the stream
+int fetch_count(ghicp_ctx* ctx, const int* d_count, int64_t* count) {
+  int* hc = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->pinned) + 320);  // pinned: see gh_bbox_dev
+  GH_HIP(hipMemcpyAsync(hc, d_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(hipStreamSynchronize(ctx->stream));
+  *count = (int64_t)(unsigned)*hc;
+  return GHICP_OK;
+}
+}  // namespace
+
+extern "C" int ghicp_scan_inclusive_u32(ghicp_ctx* ctx, uint32_t* data, int64_t n) {
+  GH_ENTER(ctx);
+  GH_ARG(n >= 0 && n < (1ll << 31) - 2 && (n == 0 || data != nullptr));
+  if (n == 0) return GHICP_OK;
+  Stager sg(ctx);
+  unsigned* d;
+  GH_TRY(sg.out(data, (size_t)n, &d));  // device-pointer mode: d == data, the caller's pointer reaches the kernels as it is
+  if (ctx->host_ptrs) GH_HIP(hipMemcpyAsync(d, data, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+  GH_TRY(gh_scan_inclusive_u32(ctx, d, n));
+  return sg.finish();
+}
+
+extern "C" int ghicp_select_flagged(ghicp_ctx* ctx, const uint8_t* flags, const uint32_t* vals, int64_t n, uint32_t* out, int64_t* count) {
+  GH_ENTER(ctx);
+  GH_ARG(n >= 0 && n < (1ll << 31) - 2 && count != nullptr && (n == 0 || (flags != nullptr && out != nullptr)));
+  GH_ARG(!ranges_overlap(out, (size_t)n * 4, flags, (size_t)n) && !ranges_overlap(out, (size_t)n * 4, vals, (size_t)n * 4));
+  *count = 0;
+  if (n == 0) return GHICP_OK;
+  Stager sg(ctx);
+  const unsigned char* f;
+  const unsigned* v = nullptr;
+  unsigned* o;
+  int* dcount;
+  GH_TRY(sg.in(flags, (size_t)n, &f));
+  if (vals) GH_TRY(sg.in(vals, (size_t)n, &v));
+  GH_TRY(sg.out(out, (size_t)n, &o));
+  GH_TRY(ctx->reserve(B_FE_SCAN, 16, &dcount));
+  if (v) GH_TRY(gh_select_flagged_u32(ctx, v, f, n, o, dcount));
+  else GH_TRY(gh_select_flagged_iota(ctx, f, n, reinterpret_cast<int*>(o), dcount));
+  GH_TRY(fetch_count(ctx, dcount, count));
+  if (!sg.outs.empty()) sg.outs.back().bytes = (size_t)*count * sizeof(unsigned);  // host-pointer mode: only out[0 .. count) is the caller's to lose
+  return sg.finish();
+}
+
+extern "C" int ghicp_unique_sorted_u32(ghicp_ctx* ctx, const uint32_t* keys, int64_t n, uint32_t* out, int64_t* count) {
+  GH_ENTER(ctx);
+  GH_ARG(n >= 0 && n < (1ll << 31) - 2 && count != nullptr && (n == 0 || (keys != nullptr && out != nullptr)));
+  GH_ARG(!ranges_overlap(out, (size_t)n * 4, keys, (size_t)n * 4));
+  *count = 0;
+  if (n == 0) return GHICP_OK;
+  Stager sg(ctx);
+  const unsigned* k;
+  unsigned* o;
+  int* dcount;
+  GH_TRY(sg.in(keys, (size_t)n, &k));
+  GH_TRY(sg.out(out, (size_t)n, &o));
+  GH_TRY(ctx->reserve(B_FE_SCAN, 16, &dcount));
+  GH_TRY(gh_unique_sorted_u32(ctx, k, n, o, dcount));
+  GH_TRY(fetch_count(ctx, dcount, count));
+  if (!sg.outs.empty()) sg.outs.back().bytes = (size_t)*count * sizeof(unsigned);
+  return sg.finish();
+}
+
 extern "C" int ghicp_sort_pairs(ghicp_ctx* ctx, int key_bytes, const void* keys_in, void* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int64_t n,
                                 int bit_begin, int bit_end) {
   GH_ENTER(ctx);
   GH_ARG((key_bytes == 4 || key_bytes == 8) && n >= 0 && n < (1ll << 31) - 2 && bit_begin >= 0 && bit_begin <= bit_end && bit_end <= 8 * key_bytes);
   GH_ARG((vals_in == nullptr) == (vals_out == nullptr) && (n == 0 || (keys_in != nullptr && keys_out != nullptr && keys_in != keys_out)));
   if (n == 0) return GHICP_OK;
+  {  // a pass scatters into an output while other workgroups still read the inputs: no output may share a byte with an input or with the other output
+    const size_t kbytes = (size_t)n * (size_t)key_bytes, vbytes = (size_t)n * sizeof(uint32_t);
+    GH_ARG(!ranges_overlap(keys_out, kbytes, keys_in, kbytes) && !ranges_overlap(keys_out, kbytes, vals_in, vbytes) && !ranges_overlap(keys_out, kbytes, vals_out, vbytes));
+    GH_ARG(!ranges_overlap(vals_out, vbytes, vals_in, vbytes) && !ranges_overlap(vals_out, vbytes, keys_in, kbytes));
+  }
   Stager sg(ctx);
   const unsigned* vi = nullptr;
   unsigned* vo = nullptr;

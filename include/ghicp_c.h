@@ -138,9 +138,19 @@ int ghicp_voxel_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, 
 /* The stable sort behind the voxel filter, the grids and the NMS order (the reference's std::sort calls, include/filter.hpp:66 and
  * include/keypoint_detect.hpp:119-130, made deterministic: equal keys keep their input order).  Ascending on the key bits
  * [bit_begin, bit_end) of n keys of key_bytes (4 or 8) bytes each; vals_in / vals_out (u32) may both be NULL (keys only).  The inputs are
- * left untouched; out-of-place (keys_out != keys_in). */
+ * left untouched.  Out of place: the four arrays (n items each) must not share a byte -- vals_out == vals_in, an output that overlaps
+ * an input or the other output, even by a partial range, is GHICP_ERR_ARG and nothing is written. */
 int ghicp_sort_pairs(ghicp_ctx* ctx, int key_bytes, const void* keys_in, void* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int64_t n,
                      int bit_begin, int bit_end);
+/* The other device-wide primitives under the front end (prims.hip), as primitives; n < 2^31 - 2 as for the sort, n == 0 is fine.
+ * Inclusive prefix sum in place, modulo 2^32: data[i] = data[0] + ... + data[i].  `data` needs the alignment of its type only. */
+int ghicp_scan_inclusive_u32(ghicp_ctx* ctx, uint32_t* data, int64_t n);
+/* out[0 .. *count) = vals[i] -- or the position i itself when vals is NULL -- of every i with flags[i] != 0 (any non-zero byte), in
+ * ascending order of i.  out: capacity n, only the first *count items are written; it may not overlap flags or vals.  *count [host]. */
+int ghicp_select_flagged(ghicp_ctx* ctx, const uint8_t* flags, const uint32_t* vals, int64_t n, uint32_t* out, int64_t* count);
+/* out[0 .. *count) = the distinct values of the ASCENDING array keys (the head of every run of equal keys), ascending.  out: capacity n,
+ * only the first *count items are written; it may not overlap keys.  *count [host]. */
+int ghicp_unique_sorted_u32(ghicp_ctx* ctx, const uint32_t* keys, int64_t n, uint32_t* out, int64_t* count);
 /* gather rows: out[i] = xyz[idx[i]] as packed float4 (x,y,z,0). */
 int ghicp_gather_points(ghicp_ctx* ctx, const float* xyz, int stride, const int32_t* idx, int64_t m, float* out_xyz4);
 /* bbx_magnitude of test/ghicp_main.cpp:91-93 (CloudUtility::getCloudBound, utility.h:153-183). [host] out */

@@ -8,12 +8,16 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "gh-icp_amd", "csrc")
-ASAN = os.environ.get("HIPSIM_ASAN") == "1"  # LD_PRELOAD=$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0
+# HIPSIM_ASAN=1: AddressSanitizer + alignment checking (a misaligned access aborts).  Load this build from an executable that is itself linked with
+# -fsanitize=address, so that the sanitizer runtime is the executable's own (tests/cpp/test_prims_sanitized.cpp, tests/test_sim_cpu.py);
+# ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0
+ASAN = os.environ.get("HIPSIM_ASAN") == "1"
 TSAN = os.environ.get("HIPSIM_TSAN") == "1"  # LD_PRELOAD=$(gcc -print-file-name=libtsan.so): lanes are TSan fibers, barriers / collectives are its sync points
 OUT_DIR = os.path.join(HERE, "_build_asan" if ASAN else ("_build_tsan" if TSAN else "_build"))
 LIB = os.path.join(OUT_DIR, "libghicp_sim.so")
+SAN_FLAGS = ["-fsanitize=address", "-fsanitize=alignment", "-fno-sanitize-recover=alignment"]
 FLAGS = ["-x", "c++", "-std=c++17", "-O2", "-g1", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-pthread", "-w", "-fno-extern-tls-init",
-         "-I", os.path.join(HERE, "include"), "-I", CSRC] + (["-fsanitize=address", "-fno-omit-frame-pointer", "-g"] if ASAN else []) + (["-fsanitize=thread", "-fno-omit-frame-pointer", "-g", "-O1"] if TSAN else [])
+         "-I", os.path.join(HERE, "include"), "-I", CSRC] + (SAN_FLAGS + ["-fno-omit-frame-pointer", "-g"] if ASAN else []) + (["-fsanitize=thread", "-fno-omit-frame-pointer", "-g", "-O1"] if TSAN else [])
 
 
 def _newer(target, deps):
@@ -53,7 +57,7 @@ def build(verbose=False):
     if failed:
         raise RuntimeError("hipsim build failed")
     if jobs or not os.path.exists(LIB):
-        subprocess.run(["g++", "-shared", "-pthread"] + (["-fsanitize=address"] if ASAN else []) + (["-fsanitize=thread"] if TSAN else []) + ["-o", LIB] + objs, check=True)
+        subprocess.run(["g++", "-shared", "-pthread"] + (SAN_FLAGS if ASAN else []) + (["-fsanitize=thread"] if TSAN else []) + ["-o", LIB] + objs, check=True)
     return LIB
 
 

@@ -38,7 +38,29 @@ def test_gpu_tests_on_the_host_simt_interpreter():
     import re
 
     m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) >= 40 and "failed" not in r.stdout, tail
+    assert m and int(m.group(1)) >= 50 and "failed" not in r.stdout, tail  # (40 + the ten tests of test_gpu_prims.py, which all run here)
+
+
+def test_prims_under_address_and_alignment_sanitizers(tmp_path):
+    """The scan / select / unique / sort primitives at the sizes and base offsets that matter for addressing (a range that starts 0..3 words
+    past a 256-byte boundary, ragged last tiles, 257 tiles, run heads on tile boundaries), driven through the C ABI by tests/cpp/test_prims_sanitized.cpp
+    against the interpreter library built with AddressSanitizer and alignment checking (HIPSIM_ASAN=1): every array is a heap block of exactly the
+    bytes a call may touch, so an access one item out of range, or a 16-byte access to a 4-byte-aligned address, aborts the program; a wrong
+    answer makes it exit 1.  The program is linked with -fsanitize=address itself: the sanitizer runtime is its own, nothing is preloaded."""
+    sim = os.path.join(ROOT, "tests", "hipsim")
+    r = subprocess.run([sys.executable, os.path.join(sim, "build.py")], env=dict(os.environ, HIPSIM_ASAN="1"), cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lib_dir = os.path.join(sim, "_build_asan")
+    assert os.path.exists(os.path.join(lib_dir, "libghicp_sim.so"))
+    exe = str(tmp_path / "test_prims_sanitized")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "cpp", "test_prims_sanitized.cpp"), "-o", exe, "-L", lib_dir, "-lghicp_sim", "-Wl,-rpath," + lib_dir, "-pthread"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    # leaks: the interpreter's lane stacks live for the process; stack-use-after-return would move the lanes' frames off their fiber stacks
+    env = dict(os.environ, HIPSIM_THREADS="2", ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:verify_asan_link_order=0")
+    r = subprocess.run([exe], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0 and "prims sanitized: ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
 
 
 def test_solver_fuzz_in_reverse_lane_order():
