@@ -55,26 +55,35 @@ struct IcpState {
 };
 
 // ------------------------------------------------------------------------------------------------ 1-NN search
+// Rounding margin of axis a: how far beyond the face mn + k * cell a point assigned to cell k may lie.  The cell of a point
+// is floor((v - mn) * inv), three float roundings plus that of cell = 1 / inv: an error of up to 2.4e-7 * k cells at cell
+// k, so the margin grows with the cells of the axis (a 0.02 m cell along a line of 400 m is 20 000 cells) on top of a
+// flat 2e-3 cell.  The rounding of mn + k * cell itself is monotone and cannot put a float on the wrong side of a face.
+__device__ inline float axis_margin(const NnGrid& G, int a) { return (2e-3f + 4e-7f * (float)G.d.dim[a]) * G.cell; }
+
 // Lower bound on the distance from p to any point in a cell outside the block [c - r, c + r]^3 (sides clipped by the
-// grid need no bound: nothing lies beyond them).  Cell assignment is a rounded float product, hence the margin.
+// grid need no bound: nothing lies beyond them).  The margin is SUBTRACTED: a point of a cell outside the block may lie
+// that far inside the block's faces.
 __device__ inline float block_reach(const NnGrid& G, float px, float py, float pz, int cx, int cy, int cz, int r) {
   float m = kInf;
   const float p[3] = {px, py, pz};
   const int c[3] = {cx, cy, cz};
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    if (c[a] - r > 0) m = fminf(m, p[a] - (G.d.mn[a] + (float)(c[a] - r) * G.cell));
-    if (c[a] + r < G.d.dim[a] - 1) m = fminf(m, (G.d.mn[a] + (float)(c[a] + r + 1) * G.cell) - p[a]);
+    const float mg = axis_margin(G, a);
+    if (c[a] - r > 0) m = fminf(m, p[a] - (G.d.mn[a] + (float)(c[a] - r) * G.cell) - mg);
+    if (c[a] + r < G.d.dim[a] - 1) m = fminf(m, (G.d.mn[a] + (float)(c[a] + r + 1) * G.cell) - p[a] - mg);
   }
-  if (m >= kInf) return kInf;
-  return m - 2e-3f * G.cell;
+  return m;
 }
 
-// squared distance from coordinate p to the cell interval [lo, hi] of one axis (cells as the grid assigns them, shrunk
-// by the same rounding margin as block_reach)
+// Lower bound on the squared distance from coordinate p to any point the grid assigns to the cells [lo, hi] of one axis.
+// Callers skip a run when this exceeds the best distance so far, so it must never over-estimate: the interval is WIDENED
+// by the margin on both sides (a point on a cell face, or a hair beyond it, may be assigned to either neighbour; when
+// every target sits on a face -- a line or a thin bar along an axis has y = z = mn -- that decides which runs are read).
 __device__ inline float axis_gap2(const NnGrid& G, int a, float p, int lo, int hi) {
-  const float m = 2e-3f * G.cell;
-  const float l = G.d.mn[a] + (float)lo * G.cell + m, h = G.d.mn[a] + (float)(hi + 1) * G.cell - m;
+  const float m = axis_margin(G, a);
+  const float l = G.d.mn[a] + (float)lo * G.cell - m, h = G.d.mn[a] + (float)(hi + 1) * G.cell + m;
   const float d = fmaxf(fmaxf(l - p, p - h), 0.f);
   return d * d;
 }
