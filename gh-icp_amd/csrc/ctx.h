@@ -172,6 +172,13 @@ struct ghicp_ctx {
   int confine_cus = 0;
   struct ConfinePair { int cus; hipStream_t confined, rest; };
   std::vector<ConfinePair> confine_cache;  // one masked stream pair per share B seen (loop.hip run_pair_loop)
+  // Compact LDS layout of the Kuhn-Munkres state (km4_dev.h: 36 instead of 44 B per row, sty and tlo in a per-slot global region, buffer
+  // B_KM_SLACK): graphs of n = 925..1131 then fit four to a CU and join the one four-per-CU class.  GHICP_KM_COMPACT=0 switches it off (the
+  // planning of round 6: A/B measurements); GHICP_KM_COMPACT_FROM=<n> is the test hook that FORCES the compact layout on every graph of n rows
+  // or more (1: on every graph), whatever LDS its slot has.
+  bool km_compact = true;
+  int km_compact_from = 0;
+  int km_kflags() const { return (km_force_hazard ? 4 : 0) | (km_compact_from << 8); }  // the solver's flag word (k4_solve_block)
   int loop_min_lds = 0;  // GHICP_LOOP_MIN_LDS=<bytes> (experiment hook): every solve slot asks for at least this much LDS, e.g. 46080 = three slots per CU with 25 KB of every CU left to other kernels
   std::vector<uint32_t> cu_mask;       // set by ghicp_ctx_set_cu_mask: the auxiliary streams are restricted to the same compute units
   std::vector<hipStream_t> aux_streams;

@@ -1,5 +1,7 @@
 // Kuhn-Munkres, fourth-generation kernel (gfx950): host side and the stand-alone solve kernel.  The solver itself is device code in
-// km4_dev.h (rules R1-R5 in its header), shared with the persistent pair loop of loop.hip.
+// km4_dev.h (rules R1-R5 in its header), shared with the persistent pair loop of loop.hip.  Class rule of a batch (gh_km4_plan): a graph
+// counts as four per CU when EITHER layout of the solver state fits a quarter of the CU's 160 KB -- the standard one (44 B per row) up to
+// n = 924, the compact one (36 B per row) up to n = 1131; larger graphs form the classes of three, two and one per CU, standard layout.
 #include "km4_dev.h"
 
 #include <algorithm>
@@ -8,19 +10,32 @@
 
 namespace {
 
-template <bool PROF>
-__global__ __launch_bounds__(K4_T) void k_km4(const Km2Problem* __restrict__ probs, int flags, int lds_bytes, unsigned long long* __restrict__ lstat,
-                                            const int* __restrict__ order) {
+// One kernel per layout: a launch whose graphs can take the compact layout (km4_dev.h) is followed by a second one of the same grid in
+// which the workgroups of those graphs run and all others return at once, so the standard kernel is the code it always was.
+template <bool PROF, bool CP>
+__global__ __launch_bounds__(K4_T, CP ? 4 : 1) void k_km4(const Km2Problem* __restrict__ probs, int flags, int lds_bytes, unsigned long long* __restrict__ lstat,
+                                                        const int* __restrict__ order, unsigned short* __restrict__ scr, long long scr_stride) {
   const Km2Problem P = probs[order ? order[blockIdx.x] : (int)blockIdx.x];
   if (P.n <= 0 || (P.done && *P.done)) return;
+  if (k4_takes_compact(P.n, flags, lds_bytes) != CP) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  k4_solve_block<PROF>(P, flags, smem, lds_bytes, lstat);
+  k4_solve_block<PROF, CP>(P, flags, smem, lds_bytes, lstat, CP && scr ? (k4_gu16)(scr + (size_t)blockIdx.x * (size_t)scr_stride) : (k4_gu16) nullptr);
 }
 
 }  // namespace
 
 // lx, ly, slack (f64) + 16 f64 of reduction scratch + 8 bitsets + SH_NUM ints + match, two stacks, listed columns and CSR offsets (u16)
-// + list lengths (u8): 44 B per row
+// + list lengths (u8): 44 B per row.  Four problems fit a CU (40 960 B each) up to n = 924.
+// Compact layout (km4_dev.h): the column stack and the CSR offsets live in a per-slot region of global memory, 36 B per row; four problems
+// fit a CU up to n = 1131 (40 949 B with the 16 B of margin; the largest graph of the 64 bench scenes).
+size_t gh_km4_lds_bytes_compact(int n) { return (size_t)k4_lds_need(n, true) + 16; }
+
+// The LDS a solve slot asks for: the standard layout unless ONLY the compact one brings the graph to four per CU.
+size_t gh_km4_slot_bytes(int n, bool compact_on) {
+  const size_t quarter = 160 * 1024 / 4, std_b = gh_km4_lds_bytes(n);
+  return (compact_on && std_b > quarter && gh_km4_lds_bytes_compact(n) <= quarter) ? gh_km4_lds_bytes_compact(n) : std_b;
+}
+
 size_t gh_km4_lds_bytes(int n) {
   const size_t nw = (size_t)(n + 31) / 32;
   return (size_t)n * 3 * 8 + 16 * 8 + 8 * nw * 4 + SH_NUM * 4 + ((size_t)n * (1 + 2 * K4_CAP) + 2 * ((size_t)n + 2)) * 2 + (size_t)n + 64;
@@ -28,39 +43,54 @@ size_t gh_km4_lds_bytes(int n) {
 
 bool gh_km4_fits(int n) { return n <= 65534 && gh_km4_lds_bytes(n) <= 160 * 1024 - 256; }
 
-static int k4_launch(ghicp_ctx* ctx, const Km2Problem* d_probs, int nprob, size_t lds, const int* d_order) {
+// n_max: the largest graph of the launch; the compact layout's global scratch is reserved when a graph of the launch can take that
+// layout: the LDS of the launch is too small for n_max in the standard one, or the forcing hook is set.  This launcher has one workgroup
+// per problem and no persistent slots, so the scratch is one region per WORKGROUP (k4_scratch_u16: sty, tlo and the hint slots, which
+// doubled the tlo part; 15.5 KB at n = 1131) -- tens of MB for thousands of large problems, and a second grid whose other workgroups
+// return at once.  Off the hot path: the pair loop (loop.hip) sizes its scratch by solve slots and branches per pair.
+static int k4_launch(ghicp_ctx* ctx, const Km2Problem* d_probs, int nprob, size_t lds, const int* d_order, int n_max) {
+  unsigned short* scr = nullptr;
+  const long long scr_stride = k4_scratch_u16(n_max);
+  if (ctx->km_compact_from > 0 || k4_lds_need(n_max, false) > (long long)lds) GH_TRY(ctx->reserve(B_KM_SLACK, (size_t)nprob * (size_t)scr_stride, &scr));
   const size_t want = 160 * 1024;
   // per device and thread safe: the attribute is cheap to set, so it is simply set before every launch
-  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-  const int kflags = ctx->km_force_hazard ? 4 : 0;  // test hook: sends one phase through the hazard fallback
+  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+  GH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km4<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+  const int kflags = ctx->km_kflags();  // test hooks: one phase through the hazard fallback; the compact layout forced
   unsigned long long* lstat = nullptr;
   if (ctx->kt_on && ctx->km_launches < ghicp_ctx::KM_LSTAT_MAX) {
     GH_TRY(ctx->reserve(B_KM_LSTAT, (size_t)ghicp_ctx::KM_LSTAT_MAX * ghicp_ctx::KM_LSTAT_W, &lstat));
     lstat += ctx->km_launches * ghicp_ctx::KM_LSTAT_W;
     int per_cu = 0;
-    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_km4<false>), K4_T, lds));
+    GH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_km4<false, false>), K4_T, lds));
     ctx->km_slots.push_back(per_cu * ctx->num_cu);
     ctx->km_launches++;
   }
   hipEvent_t kt = ctx->kt_begin(KT_KM_SOLVE);
-  if (ctx->km_stats) hipLaunchKernelGGL((k_km4<true>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order);
-  else hipLaunchKernelGGL((k_km4<false>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order);
+  if (ctx->km_stats) hipLaunchKernelGGL((k_km4<true, false>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order, scr, scr_stride);
+  else hipLaunchKernelGGL((k_km4<false, false>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order, scr, scr_stride);
+  if (scr) {  // the graphs of the launch that take the compact layout
+    if (ctx->km_stats) hipLaunchKernelGGL((k_km4<true, true>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order, scr, scr_stride);
+    else hipLaunchKernelGGL((k_km4<false, true>), dim3(nprob), dim3(K4_T), lds, ctx->stream, d_probs, kflags, (int)lds, lstat, d_order, scr, scr_stride);
+  }
   ctx->kt_end(KT_KM_SOLVE, kt);
   GH_HIP(hipGetLastError());
   return GHICP_OK;
 }
 
 int gh_km4_launch(ghicp_ctx* ctx, const Km2Problem* d_probs, int nprob, int n_max) {
-  return k4_launch(ctx, d_probs, nprob, gh_km4_lds_bytes(n_max), nullptr);
+  return k4_launch(ctx, d_probs, nprob, gh_km4_slot_bytes(n_max, ctx->km_compact), nullptr, n_max);
 }
 
-int gh_km4_plan(ghicp_ctx* ctx, const int* h_n, int nprob, Km4Plan* plan, const float* cost) {
+// The host half of the plan: classes and queue order (no device work).  Returns the first n that does not fit, 0 when all do.
+static int k4_plan_host(const int* h_n, int nprob, const float* cost, bool compact_on, Km4Plan* plan, std::vector<int>& order) {
   *plan = Km4Plan();
   std::vector<std::pair<int, int>> key((size_t)nprob);  // (problems per CU, n) per problem
   for (int i = 0; i < nprob; i++) {
     const int n = std::max(1, h_n[i]);
-    if (!gh_km4_fits(n)) return ctx->fail(GHICP_ERR_INTERNAL, "gh_km4_plan: n = %d does not fit", n);
+    if (!gh_km4_fits(n)) return n;
     // problems per CU by LDS, capped at FOUR: a solve slot is a 256-thread workgroup at 128 VGPRs, so a CU never holds more than four
     // whatever their LDS.  Rounds 2-4 capped at eight: the graphs below n = 745 then formed four more classes, each with its own launch
     // and queue, the classes took the chip in launch order (a persistent workgroup leaves only when ITS queue is dry), and the longest
@@ -69,9 +99,11 @@ int gh_km4_plan(ghicp_ctx* ctx, const int* h_n, int nprob, Km4Plan* plan, const 
     // per CU = one queue in cost order = longest-processing-time-first over (almost) the whole batch.
     // (measured and dropped, call 8: leaving 4 KB of the 160 out of the count -- n <= 902 instead of <= 924 in the four-per-CU class --
     // did not bring its CUs to four slots each: 3.3 per CU, 384 pairs/s; the rule of call 6 stays)
-    key[i] = {(int)std::min<size_t>(4, (160 * 1024) / gh_km4_lds_bytes(n)), n};
+    // A graph counts as four per CU when EITHER layout fits a quarter of the CU: with the compact layout n = 925..1131 -- seven of the 64
+    // bench scenes, until then a three-per-CU class of their own on ~100 confined CUs -- join the one class, one launch, one queue.
+    key[i] = {(int)std::min<size_t>(4, (160 * 1024) / gh_km4_slot_bytes(n, compact_on)), n};
   }
-  std::vector<int> order((size_t)nprob);
+  order.resize((size_t)nprob);
   for (int i = 0; i < nprob; i++) order[i] = i;
   // fewest per CU (largest problems) first; within a class the largest first -- or, with cost hints, the costliest first: the span of a
   // batch is bounded below by its slowest pair (112 iterations x ~50 ms on the bench scenes), so that pair must not start in the middle
@@ -88,13 +120,39 @@ int gh_km4_plan(ghicp_ctx* ctx, const int* h_n, int nprob, Km4Plan* plan, const 
     plan->begin[nc] = i; plan->count[nc] = j - i;
     int nmax = 1;  // (with cost hints the first problem of a class is its costliest, not its largest)
     for (int t = i; t < j; t++) nmax = std::max(nmax, key[order[t]].second);
-    plan->lds[nc] = gh_km4_lds_bytes(nmax);
+    // the slot's LDS: what its most demanding graph asks for in the layout it takes (below a quarter of the CU the standard layout of a
+    // smaller graph can ask for more than the compact layout of a larger one)
+    for (int t = i; t < j; t++) plan->lds[nc] = std::max(plan->lds[nc], gh_km4_slot_bytes(key[order[t]].second, compact_on));
+    plan->nmax[nc] = nmax;
     plan->per_cu[nc] = key[order[i]].first;
     for (int t = i; t < j; t++) plan->weight[nc] += (cost && cost[order[t]] > 0.f) ? (double)cost[order[t]] : (double)key[order[t]].second * (double)key[order[t]].second;
     nc++;
     i = j;
   }
   plan->nclass = nc;
+  return 0;
+}
+
+// TEST-ONLY exports (declared in km_prob.h, not part of the C ABI of include/ghicp_c.h): a CPU-testable view of the plan
+// (tests/test_km4_compact_cpu.py) -- per problem its class's slots per CU, per class its LDS -- and the LDS bytes of either layout.
+extern "C" int ghicp_km4_plan_probe(const int32_t* n, int32_t count, int32_t compact_on, int32_t* per_cu_of_problem, int64_t* lds_of_class, int32_t* nclass) {
+  if (!n || count <= 0 || !per_cu_of_problem || !lds_of_class || !nclass) return GHICP_ERR_ARG;
+  Km4Plan plan;
+  std::vector<int> order;
+  if (k4_plan_host(n, count, nullptr, compact_on != 0, &plan, order) != 0) return GHICP_ERR_ARG;
+  for (int c = 0; c < plan.nclass; c++) {
+    lds_of_class[c] = (int64_t)plan.lds[c];
+    for (int t = plan.begin[c]; t < plan.begin[c] + plan.count[c]; t++) per_cu_of_problem[order[(size_t)t]] = plan.per_cu[c];
+  }
+  *nclass = plan.nclass;
+  return GHICP_OK;
+}
+extern "C" int64_t ghicp_km4_lds_bytes(int32_t n, int32_t compact) { return (int64_t)(compact ? gh_km4_lds_bytes_compact(n) : gh_km4_lds_bytes(n)); }
+
+int gh_km4_plan(ghicp_ctx* ctx, const int* h_n, int nprob, Km4Plan* plan, const float* cost) {
+  std::vector<int> order;
+  const int bad_n = k4_plan_host(h_n, nprob, cost, ctx->km_compact, plan, order);
+  if (bad_n) return ctx->fail(GHICP_ERR_INTERNAL, "gh_km4_plan: n = %d does not fit", bad_n);
   GH_TRY(ctx->reserve(B_KM_ORDER, (size_t)nprob + 1, &plan->d_order));
   GH_HIP(hipMemcpyAsync(plan->d_order, order.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   GH_HIP(hipStreamSynchronize(ctx->stream));  // `order` is a local
@@ -103,7 +161,7 @@ int gh_km4_plan(ghicp_ctx* ctx, const int* h_n, int nprob, Km4Plan* plan, const 
 
 int gh_km4_launch_plan(ghicp_ctx* ctx, const Km2Problem* d_probs, const Km4Plan& plan) {
   for (int c = 0; c < plan.nclass; c++)
-    if (plan.count[c] > 0) GH_TRY(k4_launch(ctx, d_probs, plan.count[c], plan.lds[c], plan.d_order + plan.begin[c]));
+    if (plan.count[c] > 0) GH_TRY(k4_launch(ctx, d_probs, plan.count[c], plan.lds[c], plan.d_order + plan.begin[c], plan.nmax[c]));
   return GHICP_OK;
 }
 

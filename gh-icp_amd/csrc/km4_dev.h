@@ -1,7 +1,9 @@
 // Kuhn-Munkres, fourth-generation kernel (gfx950): the reference's result (src/km.cpp:13-126) WITHOUT stepping through the
 // reference's depth-first search wherever its outcome is order independent.  One 256-thread workgroup per problem, all
-// solver state in LDS (44 B per row: 4 problems per CU up to n = 930), the CSR of the explicit entries streamed from global
-// memory only by the bulk passes of failed phases.  Rules (oracle/km4_model.inc states them sequentially and is fuzzed against
+// solver state in LDS (44 B per row: 4 problems per CU up to n = 924; the COMPACT layout, template parameter CP, keeps the column stack
+// and the CSR offsets / hint columns in a per-slot region of global memory instead: 36 B per row, 4 problems per CU up to n = 1131 -- a
+// graph takes it when the standard layout does not fit the LDS its workgroup was given, k4_takes_compact), the CSR of the explicit entries
+// streamed from global memory only by the bulk passes of failed phases.  Rules (oracle/km4_model.inc states them sequentially and is fuzzed against
 // the reference traversal; R1 = E1-E3 of round 1's solver, whose rules E1-E12 oracle/km_model.inc still states):
 //   R2  per row a list of <= 3 columns in LDS, ascending, EXACTLY the row's tight explicit entries (fl(fl(lx+ly) - w) < eps), plus
 //       each entry's offset in its CSR row.  An explicit entry can only BECOME tight when its row label drops, i.e. for rows visited
@@ -59,11 +61,24 @@ typedef __attribute__((address_space(1))) const unsigned* k4_gu32;
 
 enum { SH_QT = 0, SH_FREE, SH_RES, SH_QTF, SH_HAZ, SH_CH0, SH_CH1, SH_BAD, SH_NF, SH_UNCERT, SH_LROW, SH_CH2, SH_DFS, SH_NUM = 16 };
 
+// The COMPACT layout (CP; graphs whose standard layout does not fit four to a CU, n = 925..1131): the two arrays the hot loops read least
+// leave LDS for a per-slot region of global memory -- the CSR offsets / hint columns (tlo: read by k4_revalidate and, for rows with
+// 4..6 tight entries, by the S rounds) and the column stack / tree edges (sty: written by every claim and descent, read when the search
+// steps back, by the augmentation and by the certificates of rule R3').  8 B per row less: 36 B per row.  The pointer TYPE carries the
+// address space, so the standard instantiation addresses LDS exactly as before and the compact one never goes through a generic pointer.
+typedef __attribute__((address_space(1))) unsigned short* k4_gu16;
+template <bool CP> struct K4Mem { typedef unsigned short* u16p; };
+template <> struct K4Mem<true> { typedef k4_gu16 u16p; };
+
+template <bool CP>
 struct K4 {
   double *lx, *ly, *slack, *red;
   unsigned *visx, *visy, *prevy, *pushed, *good, *goody, *freey, *ovf;
   int* sh;
-  unsigned short *match, *stx, *sty, *tlc, *tlo;  // tlc / tlo: listed columns and their offsets in the CSR row (K4_CAP per row)
+  unsigned short *match, *stx, *tlc;  // tlc / tlo: listed columns and their offsets in the CSR row (K4_CAP per row)
+  typename K4Mem<CP>::u16p sty, tlo;
+  typename K4Mem<CP>::u16p tlh;       // the hint columns of rows with 4..6 tight entries: the offset slots themselves (a flagged row never uses them) in
+                                      // LDS, slots of their own in the compact layout (k4_scratch_u16 counts them: the tlo region doubled)
   unsigned char* tln;
   int n, nw;
   double bg, eps;
@@ -71,6 +86,12 @@ struct K4 {
   k4_gint cols;
   k4_gf64 vals;
 };
+
+// Compact layout: values one lane of wave 0 stored to the global region and another lane of the same wave reads (the search's column
+// stack) are ordered by a workgroup fence; in LDS the wave's own instruction order does that.  Two STORES of one wave to one address
+// (sty[sp]: K4_NONE when a frame opens, its column when the frame claims one, by another lane) need no fence: a wave's vector stores
+// to one address are performed in the order it issued them.
+template <bool CP> __device__ inline void k4_gfence() { if (CP) __threadfence_block(); }
 
 __device__ inline bool k4_bit(const unsigned* b, int i) { return (b[i >> 5] >> (i & 31)) & 1u; }
 __device__ inline bool k4_flagged(int tn) { return tn > K4_CAP; }
@@ -84,8 +105,8 @@ __device__ inline int k4_cnt(int tn) { return tn > K4_CAP ? 0 : tn; }  // listed
 // column when it is the column's TREE EDGE (sty[col] = the row the flood claimed it from; certificates collect in goody, which is idle
 // between two augmenting phases); a tight entry into any other column is new: the column is claimed for the next phase's flood on the
 // spot (visited bit, tree edge, owner appended to the queue behind the `count` rows this pass reads).
-template <bool REBUILD, bool PUSH, bool ONLY_UNPUSHED, bool SEED = false>
-__device__ inline void k4_bulk(const K4& s, const unsigned short* list, int count, int wave, int lane) {
+template <bool REBUILD, bool PUSH, bool ONLY_UNPUSHED, bool SEED = false, bool CP = false>
+__device__ inline void k4_bulk(const K4<CP>& s, const unsigned short* list, int count, int wave, int lane) {
   const int grp = lane >> 4, lig = lane & 15;
   unsigned long long* sl = reinterpret_cast<unsigned long long*>(s.slack);
   for (int base = 0; base < count; base += 16) {
@@ -142,7 +163,7 @@ __device__ inline void k4_bulk(const K4& s, const unsigned short* list, int coun
           __builtin_amdgcn_wave_barrier();
           if (in && td) {
             const int rk = cnt + __popc(gb & ((1u << lig) - 1u));
-            if (rk >= K4_CAP && rk < K4_HINT) s.tlo[x * K4_CAP + rk - K4_CAP] = (unsigned short)col[j];
+            if (rk >= K4_CAP && rk < K4_HINT) s.tlh[x * K4_CAP + rk - K4_CAP] = (unsigned short)col[j];
           }
           cnt += __popc(gb);
         }
@@ -164,7 +185,8 @@ __device__ inline void k4_bulk(const K4& s, const unsigned short* list, int coun
 // that was NOT visited may have left the tight set.  Such rows re-test their entries (value through the stored CSR offset) and
 // compact their list; visited rows are rebuilt from their CSR row by the bulk pass.  Few rows qualify (the visited sets are small),
 // so the pass is an LDS sweep plus, rarely, one round of value loads.
-__device__ inline void k4_revalidate(const K4& s, int tid) {
+template <bool CP>
+__device__ inline void k4_revalidate(const K4<CP>& s, int tid) {
   // visited rows / columns of the failed phase through their copies `pushed` / `prevy`: the next phase clears visx / visy, the copies
   // stay until the next failed phase, so this pass needs no barrier of its own (the one that opens the next phase orders its writes)
   for (int base = tid; base < s.n; base += 4 * K4_T) {
@@ -215,7 +237,8 @@ __device__ inline void k4_revalidate(const K4& s, int tid) {
 // the matching, the flagged rows, the pool: n + n + 2 n u16).  Until round 6 they lived in the flood's queue and the DFS's column stack
 // (stx / sty), which the lazy S of rule R5' needs intact: S is now computed in the MIDDLE of the search.  A row with more tight entries than
 // its region holds joins S unconditionally, as before (any superset of good is valid, R5).  16 lanes per row, as in k4_bulk.
-__device__ inline void k4_pool_build(const K4& s, const unsigned short* __restrict__ flist, unsigned short* __restrict__ pool, int nf, int region, int wave, int lane) {
+template <bool CP>
+__device__ inline void k4_pool_build(const K4<CP>& s, const unsigned short* __restrict__ flist, unsigned short* __restrict__ pool, int nf, int region, int wave, int lane) {
   const int grp = lane >> 4, lig = lane & 15, capf = region - 1;
   for (int base = 0; base < nf; base += 16) {
     const int i = base + wave * 4 + grp;
@@ -299,8 +322,8 @@ __device__ inline double k4_wave_min(double v) {
     qt += __popcll(eb_);                                                                    \
   } while (0)
 
-template <bool PROF>
-__device__ inline bool k4_flood(const K4& s, int qh0, int qt0, double lflood0, int lane, int* qt_out, long long* pc) {
+template <bool PROF, bool CP>
+__device__ inline bool k4_flood(const K4<CP>& s, int qh0, int qt0, double lflood0, int lane, int* qt_out, long long* pc) {
   const int n = s.n;
   int qh = qh0, qt = qt0;
   bool free_l = false;
@@ -397,8 +420,8 @@ struct K4Dfs {
 // Returns 1: augmented; 0: internal error; 2 (only with lazy): the search is about to take its first step back -- D holds its state, the
 // stacks stx / sty its frames; the caller computes S, cuts the stack back to its deepest good frame (k4_dfs_unwind) and calls again with
 // lazy = false.  A fresh search: D.sp = 0, D.x = root, D.ystart = 0, D.ck = NaN (never matches), D.cp = D.cnext = 0, stx[0] = root.
-template <bool PROF>
-__device__ inline int k4_dfs(const K4& s, K4Dfs& D, const bool lazy, int lane, long long* q_iter, long long* q_act, long long* pd) {
+template <bool PROF, bool CP>
+__device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lane, long long* q_iter, long long* q_act, long long* pd) {
   const int n = s.n;
   const double bg = s.bg, eps = s.eps;
   int sp = D.sp, x = D.x, ystart = D.ystart;
@@ -543,6 +566,7 @@ __device__ inline int k4_dfs(const K4& s, K4Dfs& D, const bool lazy, int lane, l
       }
       sp--;
       if (sp < 0) return 0;
+      k4_gfence<CP>();  // the column lane 0 stored when this frame descended
       x = s.stx[sp]; ystart = (int)s.sty[sp] + 1;
       if (PROF) { pd[4]++; pd[9] += (long long)__builtin_readcyclecounter() - t_it0; }
     }
@@ -550,6 +574,7 @@ __device__ inline int k4_dfs(const K4& s, K4Dfs& D, const bool lazy, int lane, l
   }
   // augment: match[y] = x on every level of the recursion (km.cpp:26-29); the last column is no longer free
   __builtin_amdgcn_wave_barrier();
+  k4_gfence<CP>();
   const int ylast = s.sty[sp];
   for (int f = lane; f <= sp; f += 64) s.match[s.sty[f]] = s.stx[f];
   if (lane == 0) atomicAnd(&s.freey[ylast >> 5], ~(1u << (ylast & 31)));
@@ -561,7 +586,8 @@ __device__ inline int k4_dfs(const K4& s, K4Dfs& D, const bool lazy, int lane, l
 // frames are cut from the first row outside S on.  The search then goes on after the column that frame was waiting on; if every frame's
 // row is in S the same row is looked at again, now under S.  Returns false when the root itself is outside S (impossible: the flood
 // reached a free column from it).
-__device__ inline bool k4_dfs_unwind(const K4& s, K4Dfs& D, int lane) {
+template <bool CP>
+__device__ inline bool k4_dfs_unwind(const K4<CP>& s, K4Dfs& D, int lane) {
   int keep = D.sp + 1;
   for (int base = 0; base <= D.sp; base += 64) {
     const int f = base + lane;
@@ -582,7 +608,8 @@ __device__ inline bool k4_dfs_unwind(const K4& s, K4Dfs& D, int lane) {
 // A matrix that gets here has an edge within an ulp of eps after a relabelling; the reference itself usually does not
 // terminate on such input (its delta becomes 0), hence the step budget (the O(n^3) bound of a legitimate instance).  Slow by design,
 // never on the hot path.
-__device__ inline int k4_literal(const K4& s, const Km2Problem& P) {
+template <bool CP>
+__device__ inline int k4_literal(const K4<CP>& s, const Km2Problem& P) {
   const int n = s.n;
   const double bg = s.bg, eps = s.eps;
   unsigned short* curs = s.tlc;  // per frame: CSR cursor relative to the row start (n entries of the 3n available)
@@ -648,13 +675,28 @@ __device__ inline int k4_literal(const K4& s, const Km2Problem& P) {
   return 0;
 }
 
-// One solve by the calling 256-thread workgroup: `smem` = lds_bytes of LDS (gh_km4_lds_bytes(P.n) at least), every thread of the
-// workgroup must call.  Shared by the stand-alone kernel k_km4 (km4.hip) and the persistent pair loop (loop.hip).
-template <bool PROF>
-__device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem, int lds_bytes, unsigned long long* __restrict__ lstat) {
+// Bytes of LDS a solve of n rows touches, without the margin gh_km4_lds_bytes adds; compact: without sty and tlo (36 instead of 44 B per row).
+__host__ __device__ inline long long k4_lds_need(int n, bool compact) {
+  const long long nw = (n + 31) / 32, u16s = compact ? 5ll * n + 2 : 9ll * n + 4;
+  return 24ll * n + 16 * 8 + 32 * nw + SH_NUM * 4 + 2 * u16s + n;
+}
+// u16 of global scratch per solve slot in the compact layout: sty (n + 2), tlo and the hint slots (K4_CAP per row each)
+__host__ __device__ inline long long k4_scratch_u16(int n) { return ((long long)n * (1 + 2 * K4_CAP) + 2 + 63) & ~63ll; }
+// The layout a solve takes: the standard one whenever it fits the LDS the workgroup was given; flags >> 8 = n from which the compact layout
+// is FORCED (test hook GHICP_KM_COMPACT_FROM, 0 = never).
+__device__ inline bool k4_takes_compact(int n, int flags, int lds_bytes) {
+  const int from = flags >> 8;
+  return (from > 0 && n >= from) || k4_lds_need(n, false) > (long long)lds_bytes;
+}
+
+// One solve by the calling 256-thread workgroup: `smem` = lds_bytes of LDS (gh_km4_lds_bytes(P.n) at least, gh_km4_lds_bytes_compact(P.n)
+// with CP), every thread of the workgroup must call.  CP: `scr` = k4_scratch_u16(P.n) u16 of global memory that belong to this workgroup
+// for the time of the call.  Shared by the stand-alone kernel k_km4 (km4.hip) and the persistent pair loop (loop.hip).
+template <bool PROF, bool CP>
+__device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem, int lds_bytes, unsigned long long* __restrict__ lstat, k4_gu16 scr) {
   const unsigned long long t_wall0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;  // 100 MHz, common to all CUs
   const int n = P.n, nw = (n + 31) / 32, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  K4 s;
+  K4<CP> s;
   s.n = n; s.nw = nw; s.bg = P.bg; s.eps = P.eps;
   s.rptr = (k4_gu32)P.row_ptr; s.cols = (k4_gint)P.cols; s.vals = (k4_gf64)P.vals;
   s.lx = (double*)smem;
@@ -667,12 +709,21 @@ __device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem
   s.sh = (int*)(s.ovf + nw);
   s.match = (unsigned short*)(s.sh + SH_NUM);
   s.stx = s.match + n;
-  s.sty = s.stx + n + 2;
-  s.tlc = s.sty + n + 2;
-  s.tlo = s.tlc + (size_t)n * K4_CAP;
-  s.tln = (unsigned char*)(s.tlo + (size_t)n * K4_CAP);
-  if ((long long)(reinterpret_cast<char*>(s.tln + n) - smem) > (long long)lds_bytes) {  // the launch gave this workgroup less LDS than the
-    if (tid == 0 && P.status) *P.status = 6;                                            // problem needs: refuse loudly, touch nothing
+  if constexpr (CP) {
+    s.tlc = s.stx + n + 2;
+    s.tln = (unsigned char*)(s.tlc + (size_t)n * K4_CAP);
+    s.sty = scr;
+    s.tlo = scr + n + 2;
+    s.tlh = s.tlo + (size_t)n * K4_CAP;
+  } else {
+    s.sty = s.stx + n + 2;
+    s.tlc = s.sty + n + 2;
+    s.tlo = s.tlc + (size_t)n * K4_CAP;
+    s.tlh = s.tlo;
+    s.tln = (unsigned char*)(s.tlo + (size_t)n * K4_CAP);
+  }
+  if ((long long)(reinterpret_cast<char*>(s.tln + n) - smem) > (long long)lds_bytes || (CP && scr == nullptr)) {  // the launch gave this workgroup less LDS
+    if (tid == 0 && P.status) *P.status = 6;                                            // (or no scratch) than the problem needs: refuse loudly, touch nothing
     for (int i = tid; i < n; i += K4_T) P.match_out[i] = -1;
     return;
   }
@@ -687,7 +738,10 @@ __device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem
   const long long t_begin = PROF ? (long long)__builtin_readcyclecounter() : 0;
 
   for (int i = tid; i < n; i += K4_T) { s.lx[i] = P.lx_init[i]; s.ly[i] = 0.0; s.match[i] = (unsigned short)K4_NONE; s.tln[i] = 0; }
-  for (int i = tid; i < n * K4_CAP; i += K4_T) { s.tlc[i] = 0; s.tlo[i] = 0; }  // list slots are read unconditionally: keep them valid
+  for (int i = tid; i < n * K4_CAP; i += K4_T) {  // list slots are read unconditionally: keep them valid (compact: offsets and hints are
+    s.tlc[i] = 0;                                   // only read for entries a rebuild of this solve has written)
+    if (!CP) s.tlo[i] = 0;
+  }
   for (int w = tid; w < nw; w += K4_T) {
     unsigned all = ~0u;
     if (w == nw - 1 && (n & 31)) all = (1u << (n & 31)) - 1u;
@@ -882,13 +936,18 @@ __device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem
             const int xc = min(xx[k], n - 1);
             gdw[k] = s.good[xc >> 5]; lxv[k] = s.lx[xc]; tn[k] = s.tln[xc];
 #pragma unroll
-            for (int e = 0; e < K4_CAP; e++) { lc[k][e] = s.tlc[xc * K4_CAP + e]; lc[k][K4_CAP + e] = s.tlo[xc * K4_CAP + e]; }
+            for (int e = 0; e < K4_CAP; e++) {
+              lc[k][e] = s.tlc[xc * K4_CAP + e];
+              // global: only the hints the rebuild wrote (tn - K4_CAP of them; the rest of the region is whatever an earlier solve left), 0 otherwise
+              if (CP) lc[k][K4_CAP + e] = (tn[k] > K4_CAP + e && tn[k] <= K4_HINT) ? (int)s.tlh[xc * K4_CAP + e] : 0;
+              else lc[k][K4_CAP + e] = s.tlh[xc * K4_CAP + e];
+            }
           }
           unsigned gyw[2][K4_HINT];
 #pragma unroll
           for (int k = 0; k < 2; k++)
 #pragma unroll
-            for (int e = 0; e < K4_HINT; e++) gyw[k][e] = s.goody[lc[k][e] >> 5];  // (a listed row's slots 4..6 hold CSR offsets: < n, any word will do)
+            for (int e = 0; e < K4_HINT; e++) gyw[k][e] = s.goody[lc[k][e] >> 5];  // (a listed row's slots 4..6 hold CSR offsets: < n, any word will do; compact layout: 0 where the row has no hint)
 #pragma unroll
           for (int k = 0; k < 2; k++) {
             if (xx[k] >= n) continue;

@@ -598,7 +598,15 @@ __device__ __noinline__ void pl_graph(const LoopProb& P, int* ired) {
 template <bool PROF>
 __device__ __noinline__ void pl_km(const Km2Problem* desc, int km_flags, char* smem, int lds_bytes) {
   const Km2Problem KP = *desc;
-  k4_solve_block<PROF>(KP, km_flags, smem, lds_bytes, nullptr);
+  k4_solve_block<PROF, false>(KP, km_flags, smem, lds_bytes, nullptr, (k4_gu16) nullptr);
+  __syncthreads();
+}
+// the compact layout (graphs whose standard layout does not fit the slot's LDS: n = 925..1131 at four slots per CU), a call of its own so
+// that the 89 % of the pairs below run the code they always ran
+template <bool PROF>
+__device__ __noinline__ void pl_km_compact(const Km2Problem* desc, int km_flags, char* smem, int lds_bytes, k4_gu16 scr) {
+  const Km2Problem KP = *desc;
+  k4_solve_block<PROF, true>(KP, km_flags, smem, lds_bytes, nullptr, scr);
   __syncthreads();
 }
 template <int FT>
@@ -610,7 +618,8 @@ __device__ __noinline__ void pl_solve(const LoopProb& P, double* red, int* ired,
 template <int FT, bool PROF>
 __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restrict__ probs, const int* __restrict__ order, const int npairs, int* qhead,
                                                   const int km_flags, const int lds_bytes, unsigned long long* lstat, int* progress,
-                                                  const int* __restrict__ order2, const int npairs2, int* qhead2) {
+                                                  const int* __restrict__ order2, const int npairs2, int* qhead2,
+                                                  unsigned short* __restrict__ scr, const long long scr_stride) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sB = reinterpret_cast<double*>(smem);
   double* red = sB + CHUNK_MAX * 3;
@@ -648,7 +657,11 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
       pl_sweep<FT>(P, sB, red);   // calED + calCD_* + sums + penalty (ghicp_reg.cpp:114-139, 216-341)
       pl_graph<FT>(P, ired);      // the sparse graph of findcorrespondenceKM (ghicp_reg.cpp:348-365): count, scan, fill
       const unsigned long long t0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;
-      pl_km<PROF>(P.km_desc, km_flags, smem, lds_bytes);  // Km::kmsolve (km.cpp:40-126)
+      // Km::kmsolve (km.cpp:40-126); the layout per pair from its n (scr: this slot's region of the compact layout's global scratch)
+      if (k4_takes_compact(P.C.n, km_flags, lds_bytes))
+        pl_km_compact<PROF>(P.km_desc, km_flags, smem, lds_bytes, scr ? (k4_gu16)(scr + (size_t)blockIdx.x * (size_t)scr_stride) : (k4_gu16) nullptr);
+      else
+        pl_km<PROF>(P.km_desc, km_flags, smem, lds_bytes);
       if (lstat) {
         const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t0;
         t_solve += dt; t_solve_max = dt > t_solve_max ? dt : t_solve_max; n_solve++;
@@ -744,7 +757,27 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
   const bool prof = ctx->km_stats;
   const void* fn = prof ? reinterpret_cast<const void*>(&k_pair_loop<FT, true>) : reinterpret_cast<const void*>(&k_pair_loop<FT, false>);
   GH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  const int kflags = ctx->km_force_hazard ? 4 : 0;  // test hook: sends one phase through the hazard fallback
+  const int kflags = ctx->km_kflags();  // test hooks: one phase through the hazard fallback; the compact layout forced
+  // global scratch of the compact Kuhn-Munkres layout: one region per solve slot (sized by slots, not by pairs), a range of its own for every
+  // launch of the batch (a class is launched twice when its queue is also served from the confined CUs); only when a graph can take that layout
+  unsigned short* scr = nullptr;
+  long long scr_stride = 0;
+  size_t scr_next = 0;  // slots handed out
+  {
+    int n_all = 1;
+    bool need = ctx->km_compact_from > 0;
+    for (int c = 0; c < nc; c++) {
+      n_all = std::max(n_all, plan.nmax[c]);
+      const size_t lds = std::max(std::max(plan.lds[c], (size_t)PL_SCRATCH + 64), (size_t)ctx->loop_min_lds);
+      need = need || k4_lds_need(plan.nmax[c], false) > (long long)lds;
+    }
+    if (need) {
+      scr_stride = k4_scratch_u16(n_all);
+      size_t slots = 0;
+      for (int c = 0; c < nc; c++) slots += 2 * (size_t)std::min(plan.count[c], 4 * ctx->num_cu);
+      GH_TRY(ctx->reserve(B_KM_SLACK, slots * (size_t)scr_stride, &scr));
+    }
+  }
   GH_HIP(hipMemsetAsync(dqheads, 0, 16 * sizeof(int), s));
   // one launch record per BATCH: the classes of a batch share it (first slot start, last slot end, sums over all slots), and the batch's
   // capacity is what can be resident at once: all its workgroups, but not more than the slots of the roomiest class (the classes compete
@@ -833,12 +866,14 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
     const int* o2 = steal ? (const int*)(plan.d_order + plan.begin[1]) : (const int*)nullptr;
     const int n2 = steal ? plan.count[1] : 0;
     int* q2 = steal ? dqheads + 1 : (int*)nullptr;
+    unsigned short* scr_c = scr ? scr + scr_next * (size_t)scr_stride : nullptr;
+    scr_next += (size_t)grid;
     if (prof)
       hipLaunchKernelGGL((k_pair_loop<FT, true>), dim3(grid), dim3(K4_T), lds, sc, dprobs, (const int*)(plan.d_order + plan.begin[c]), plan.count[c],
-                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2);
+                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride);
     else
       hipLaunchKernelGGL((k_pair_loop<FT, false>), dim3(grid), dim3(K4_T), lds, sc, dprobs, (const int*)(plan.d_order + plan.begin[c]), plan.count[c],
-                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2);
+                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride);
     ctx->kt_end_on(KT_PAIR_LOOP_DISPATCH, kd, sc);
     GH_HIP_JOIN(hipGetLastError());
     if (c > 0 || confined) {
@@ -847,13 +882,15 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
     }
     if (confined && c == 1 && !stole) {  // ... and the four-per-CU class once more, on the confined CUs, after the three-per-CU class (only when that class's slots could not take the queue over themselves)
       const int grid2 = std::min(plan.count[c], per_cu * confine_b);
+      unsigned short* scr_c2 = scr ? scr + scr_next * (size_t)scr_stride : nullptr;
+      scr_next += (size_t)grid2;
       hipEvent_t kd2 = ctx->kt_begin_on(KT_PAIR_LOOP_DISPATCH, ctx->confine_stream);
       if (prof)
         hipLaunchKernelGGL((k_pair_loop<FT, true>), dim3(grid2), dim3(K4_T), lds, ctx->confine_stream, dprobs, (const int*)(plan.d_order + plan.begin[c]),
-                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr);
+                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride);
       else
         hipLaunchKernelGGL((k_pair_loop<FT, false>), dim3(grid2), dim3(K4_T), lds, ctx->confine_stream, dprobs, (const int*)(plan.d_order + plan.begin[c]),
-                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr);
+                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride);
       ctx->kt_end_on(KT_PAIR_LOOP_DISPATCH, kd2, ctx->confine_stream);
       GH_HIP_JOIN(hipGetLastError());
       batch_grid += grid2;
