@@ -225,9 +225,10 @@ class Context:
 
     def pair_loop_stats(self):
         """dict of the persistent pair loop's launch records collected since kernel_timing(True) (ghicp_ctx_pair_loop_stats)."""
-        out = (C.c_double * 8)()
+        out = (C.c_double * 12)()
         self._check(self.lib.ghicp_ctx_pair_loop_stats(self.h, out))
-        keys = ("launches", "slots", "solves", "mean_solve_ms", "longest_solve_ms", "mean_launch_span_ms", "idle_slot_fraction", "solve_share_of_slot_time")
+        keys = ("launches", "slots", "solves", "mean_solve_ms", "longest_solve_ms", "mean_launch_span_ms", "idle_slot_fraction", "solve_share_of_slot_time",
+                "sweep_ms_per_iteration", "graph_ms_per_iteration", "tail_ms_per_iteration")
         return dict(zip(keys, (float(v) for v in out)))
 
     def loop_progress(self):

@@ -70,7 +70,7 @@ enum BufSlot {
   // pair pipeline
   B_P_KEEP_S, B_P_KEEP_T, B_P_DS_S, B_P_DS_T, B_P_KP_S, B_P_KP_T, B_P_KPXYZ_S, B_P_KPXYZ_T, B_P_FEAT_S, B_P_FEAT_T, B_P_LCS,
   B_P_FD, B_P_MISC, B_P_PATTERN, B_FD_JOBS, B_TRANSFORM_JOBS,
-  B_KM_LX, B_KM_MISC, B_KM_SLACK, B_KM_LSTAT, B_KM_ORDER,
+  B_KM_LX, B_KM_MISC, B_KM_SLACK, B_KM_LSTAT, B_KM_ORDER, B_KM_MASK,
   // batched front end (batch.hip)
   B_FB_DESC, B_FB_HEADPOS, B_FB_DS, B_FB_ORD,
   // hand-written scan / select primitives (prims.hip): tile totals; round-based NMS of the batched front end (batch.hip)
@@ -135,9 +135,10 @@ struct ghicp_ctx {
   }
   // per-launch statistics of the Kuhn-Munkres solve launches (collected while kernel timing is on): device records of
   // KM_LSTAT_MAX launches x KM_LSTAT_W words, and the solve slots (resident workgroups) each launch had.  Words: first start, last end,
-  // sum and max of the solve times, solves; persistent pair loop only: sum of the slot lifetimes, slots that ran
+  // sum and max of the solve times, solves; persistent pair loop only: sum of the slot lifetimes, slots that ran, (spare), and the sums of the
+  // time in the statistics sweep, in the graph build and in the tail after the solve (words 8..10)
   static constexpr int KM_LSTAT_MAX = 8192;
-  static constexpr int KM_LSTAT_W = 8;
+  static constexpr int KM_LSTAT_W = 12;
   long long km_launches = 0;
   std::vector<int> km_slots;
   long long loop_hazards = 0;            // Kuhn-Munkres solves of this context's batched loops that took the literal fallback of rule R4 (ghicp_ctx_loop_hazards)
@@ -179,6 +180,10 @@ struct ghicp_ctx {
   bool km_compact = true;
   int km_compact_from = 0;
   int km_kflags() const { return (km_force_hazard ? 4 : 0) | (km_compact_from << 8); }  // the solver's flag word (k4_solve_block)
+  // Persistent pair loop: ONE combined-distance pass per iteration decides the graph's membership while it takes the sums behind CDmean / CDstd
+  // (row bitmask in a per-slot region of global memory, buffer B_KM_MASK), and the fill reads the mask.  GHICP_LOOP_FUSE=0 runs the three passes
+  // of before (sweep with the row arg-min, count, fill): A/B measurements and tests/test_gpu_loop_fused.py.
+  bool loop_fuse = true;
   int loop_min_lds = 0;  // GHICP_LOOP_MIN_LDS=<bytes> (experiment hook): every solve slot asks for at least this much LDS, e.g. 46080 = three slots per CU with 25 KB of every CU left to other kernels
   std::vector<uint32_t> cu_mask;       // set by ghicp_ctx_set_cu_mask: the auxiliary streams are restricted to the same compute units
   std::vector<hipStream_t> aux_streams;

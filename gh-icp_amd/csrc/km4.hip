@@ -203,7 +203,8 @@ extern "C" int ghicp_ctx_km_launch_stats(ghicp_ctx* ctx, double* out8) {
 // [5] mean batch span ms (first slot start -> last slot end), [6] idle-slot fraction = 1 - sum(slot lifetimes) / sum(capacity x span),
 // capacity = the slots one class can keep resident (the classes compete for the same CUs; a slot is busy from its start to the moment
 // its queue is empty, so what is idle is the tail of a batch, when the last pairs iterate alone), [7] share of the slot lifetimes spent
-// inside Kuhn-Munkres solves (the rest: sweeps, graph build, rigid solve).
+// inside Kuhn-Munkres solves (the rest: sweeps, graph build, rigid solve), [8] [9] [10] mean ms per pair-iteration (= per solve) in the
+// statistics sweep, in the graph build (count, scan, fill) and in the tail after the solve (correspondences, rigid solve), [11] 0.
 extern "C" int ghicp_ctx_loop_hazards(ghicp_ctx* ctx, int64_t* solves) {
   GH_ENTER(ctx);
   GH_ARG(solves != nullptr);
@@ -211,10 +212,11 @@ extern "C" int ghicp_ctx_loop_hazards(ghicp_ctx* ctx, int64_t* solves) {
   return GHICP_OK;
 }
 
-extern "C" int ghicp_ctx_pair_loop_stats(ghicp_ctx* ctx, double* out8) {
+extern "C" int ghicp_ctx_pair_loop_stats(ghicp_ctx* ctx, double* out12) {
   GH_ENTER(ctx);
-  GH_ARG(out8 != nullptr);
-  for (int i = 0; i < 8; i++) out8[i] = 0.0;
+  GH_ARG(out12 != nullptr);
+  double* const out8 = out12;
+  for (int i = 0; i < 12; i++) out12[i] = 0.0;
   const long long nl = ctx->km_launches;
   if (nl <= 0 || !ctx->buf[B_KM_LSTAT].p) return GHICP_OK;
   for (hipStream_t a : ctx->aux_streams) GH_HIP(hipStreamSynchronize(a));
@@ -223,16 +225,18 @@ extern "C" int ghicp_ctx_pair_loop_stats(ghicp_ctx* ctx, double* out8) {
   std::vector<unsigned long long> h((size_t)nl * W);
   GH_HIP(hipMemcpy(h.data(), ctx->buf[B_KM_LSTAT].p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   const double tick_ms = 1e3 / 100e6;
-  double launches = 0, slots = 0, solves = 0, sum_dt = 0, mx = 0, sum_span = 0, life = 0, cap = 0;
+  double launches = 0, slots = 0, solves = 0, sum_dt = 0, mx = 0, sum_span = 0, life = 0, cap = 0, stage[3] = {0, 0, 0};
   for (long long l = 0; l < nl; l++) {
     const unsigned long long* r = &h[(size_t)l * W];
     if (r[6] == 0) continue;
     const double start = (double)((1ull << 62) - r[0]), span = (double)r[1] - start;
     launches++; slots += (double)r[6]; solves += (double)r[4]; sum_dt += (double)r[2]; mx = std::max(mx, (double)r[3]);
     sum_span += span; life += (double)r[5]; cap += std::min((double)ctx->km_slots[(size_t)l], (double)r[6]) * span;
+    for (int k = 0; k < 3; k++) stage[k] += (double)r[8 + k];
   }
   if (launches == 0) return GHICP_OK;
   out8[0] = launches; out8[1] = slots; out8[2] = solves; out8[3] = solves > 0 ? sum_dt / solves * tick_ms : 0.0; out8[4] = mx * tick_ms;
   out8[5] = sum_span / launches * tick_ms; out8[6] = cap > 0 ? 1.0 - life / cap : 0.0; out8[7] = life > 0 ? sum_dt / life : 0.0;
+  for (int k = 0; k < 3; k++) out12[8 + k] = solves > 0 ? stage[k] / solves * tick_ms : 0.0;
   return GHICP_OK;
 }

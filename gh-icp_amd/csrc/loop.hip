@@ -148,6 +148,17 @@ __global__ __launch_bounds__(ROWS) void k_cd_rowmin(const LoopProb* __restrict__
   dev_cd_rowmin<FT, COLS>(P, (int)blockIdx.x, (int)blockIdx.y, sB, red);
 }
 
+// The penalty of iterations 2, 3, ... of the BSC and FPFH energies (ghicp_reg.cpp:274-283, 326-331): from the state the PREVIOUS iteration
+// left, not from this iteration's sweep.  One function for dev_penalty and for the persistent loop's fused sweep, which needs the value
+// before the sums exist: the same expression, the same bits.
+__device__ inline double gh_penalty_from_state(const LoopState* st, const LoopConst& C, const double* wfdtab, const int it) {
+  if (C.feature == GHICP_FEATURE_BSC) {
+    const double wfd = wfdtab[it], wed = 1.0 - wfd;
+    return fmax(st->RMS * st->para1 * (double)C.scale * wed + (st->FDM + st->para2 * st->FDstd) * wfd, 5.0);
+  }
+  return st->RMS * st->para1 * (double)C.scale * st->para2;
+}
+
 // calCD_* tails: CDmean, CDstd, penalty (ghicp_reg.cpp:228-239, 264-287, 317-335)
 __device__ inline void dev_penalty(const LoopProb& P, double* red) {
   LoopState* st = P.st;
@@ -175,13 +186,11 @@ __device__ inline void dev_penalty(const LoopProb& P, double* red) {
       pen = fmax(mean, 1.0);  // Q6: line 239 overrides 230-237
       st->CDstd = 0;
     } else if (C.feature == GHICP_FEATURE_BSC) {
-      const double wfd = P.wfd[it], wed = 1.0 - wfd;
-      if (it > 1) pen = st->RMS * st->para1 * (double)C.scale * wed + (st->FDM + st->para2 * st->FDstd) * wfd;
-      else pen = mean - C.penalty_initial * sd;
-      pen = fmax(pen, 5.0);
+      if (it > 1) pen = gh_penalty_from_state(st, C, P.wfd, it);
+      else pen = fmax(mean - C.penalty_initial * sd, 5.0);
       st->CDstd = sd;
     } else {
-      if (it > 1) pen = st->RMS * st->para1 * (double)C.scale * st->para2;
+      if (it > 1) pen = gh_penalty_from_state(st, C, P.wfd, it);
       else pen = mean / C.penalty_initial;
       st->CDstd = 0;
     }
@@ -595,6 +604,215 @@ __device__ __noinline__ void pl_graph(const LoopProb& P, int* ired) {
   for (int bx = 0; bx < rb4; bx++) dev_km_csr<FT, 1>(P, bx);
   __syncthreads();
 }
+// ---- The persistent loop's own stages for the Kuhn-Munkres path (GHICP_LOOP_FUSE, default on; DESIGN.md §6 "One combined-distance pass").
+// pl_sweep / pl_graph above evaluate CD(i, j) three times per iteration for all K_S x K_T pairs (sums, count, fill) and keep a row arg-min
+// that only NN / NNR read.  Here: ONE pass takes the sums -- same block coordinates, same thread per row, same pivot, same order of the
+// additions, same gh_block_sum into the same psum slots, so CDmean, CDstd and the penalty keep their bits -- and, from iteration 2 on, when
+// the penalty follows from the previous iteration's state alone (gh_penalty_from_state), decides cd < penalty on the way: per row the count
+// and max(-cd) (order free, hence exact) and one bit per (i, j) in a row bitmask.  The fill reads the mask: wave-uniform words, no compare,
+// no ballot, 64-column blocks without a member skipped unread; CD is evaluated for the value with the expression text of dev_km_csr.
+// Iterations 0 and 1 and the feature NONE need the sweep's mean first: there the count pass runs as before and writes the mask as well.
+// Mask: 32-bit words, word w of row i at mask[w * ks + i] (the sweep's lanes are consecutive rows: coalesced stores), 2 ceil(kt / 64) words
+// per row so that the fill reads whole 64-column blocks; all of them are written in every iteration (nothing of an earlier pair is read).
+// kpT is staged in LDS once per iteration, behind the stage scratch, when the slot's LDS holds it (else chunk by chunk, as pl_sweep does).
+constexpr int PL_KPT_OFF = (PL_SCRATCH + 15) & ~15;
+
+template <int FT, typename V>
+__device__ inline double combined_distance_v(double ed, V f, double wed, double wfd, double inv_k) {
+  if (FT == GHICP_FEATURE_BSC) return wed * ed + wfd * (double)f;     // ghicp_reg.cpp:259
+  if (FT == GHICP_FEATURE_FPFH) return 1.0 * ed / pow((double)f, inv_k);  // ghicp_reg.cpp:308
+  return ed;                                                             // ghicp_reg.cpp:224
+}
+template <int FT> struct FdType { typedef uint16_t T; };
+template <> struct FdType<GHICP_FEATURE_FPFH> { typedef float T; };
+
+template <int FT, bool MEMB>
+__device__ __noinline__ void pl_sweep_km(const LoopProb& P, double* sB, double* red, double* sT, unsigned* mask) {
+  typedef typename FdType<FT>::T fd_t;
+  const LoopConst& C = P.C;
+  const int ks = C.ks, kt = C.kt, chunk = C.chunk_b, nchunk = C.nchunk_b;
+  const int rbA = cdiv_dev(ks > 0 ? ks : 1, ROWS);
+  const int it = P.st->it;
+  const fd_t* F = reinterpret_cast<const fd_t*>(P.FDt);
+  double wfd = 0, wed = 1;
+  if (FT == GHICP_FEATURE_BSC) { wfd = P.wfd[it]; wed = 1.0 - wfd; }
+  const double inv_k = 1.0 / (double)(it + 1);
+  const double dscale = (double)C.scale;
+  const double piv = cd_pivot<FT>(P, wed, wfd, inv_k);
+  const double pen = MEMB ? gh_penalty_from_state(P.st, C, P.wfd, it) : 0.0;
+  const int nw32 = 2 * cdiv_dev(kt, 64);
+  if (sT) {  // (the slot's LDS is the solver's between two iterations: staged again every time)
+    __syncthreads();
+    for (int t = threadIdx.x; t < kt * 3; t += ROWS) sT[t] = P.kpT[t];
+    __syncthreads();
+  }
+  for (int by = 0; by < nchunk; by++) {
+    const int jb = by * chunk;
+    const int je = min(kt, jb + chunk);
+    if (sT == nullptr) {
+      __syncthreads();
+      for (int t = threadIdx.x; t < (je - jb) * 3; t += ROWS) sB[t] = P.kpT[(size_t)jb * 3 + t];
+      __syncthreads();
+    }
+    const double* tB = sT ? sT + (size_t)jb * 3 : sB;
+    const int jw = (MEMB && by == nchunk - 1) ? nw32 * 32 : je;  // the last chunk also writes the words beyond kt (no member)
+    for (int bx = 0; bx < rbA; bx++) {
+      const int a = bx * ROWS + threadIdx.x;
+      double s = 0, s2 = 0;
+      if (a < ks) {
+        const double ax = P.kpS[(size_t)a * 3], ay = P.kpS[(size_t)a * 3 + 1], az = P.kpS[(size_t)a * 3 + 2];
+        unsigned cnt = 0;
+        double mx = -pen;
+        if (MEMB && by > 0) { cnt = P.km_cnt[a]; mx = P.km_lx[a]; }  // this thread's own stores of the chunk before
+        for (int j0 = jb; j0 < jw; j0 += 32) {
+          unsigned bits = 0;
+          if (j0 + 32 <= je) {
+            // a full word: the feature distances of 4 columns in flight per wait, then 4 evaluations in the order of the columns (8: spills)
+            for (int u0 = 0; u0 < 32; u0 += 4) {
+              fd_t f[4];
+              if (FT != GHICP_FEATURE_NONE) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) f[k] = F[(size_t)(j0 + u0 + k) * ks + a];
+              }
+#pragma unroll
+              for (int k = 0; k < 4; k++) {
+                const int jj = j0 + u0 + k - jb;
+                const double dx = ax - tB[jj * 3], dy = ay - tB[jj * 3 + 1], dz = az - tB[jj * 3 + 2];
+                const double ed = dscale * sqrt(dx * dx + dy * dy + dz * dz);  // ghicp_reg.cpp:122
+                const double cd = combined_distance_v<FT>(ed, FT != GHICP_FEATURE_NONE ? f[k] : (fd_t)0, wed, wfd, inv_k);
+                const double c0 = cd - piv;
+                s += c0;
+                s2 += c0 * c0;
+                if (MEMB && cd < pen) { bits |= 1u << (u0 + k); cnt++; mx = fmax(mx, -cd); }
+              }
+            }
+          } else {
+            for (int j = j0; j < je; j++) {
+              const int jj = j - jb;
+              const double dx = ax - tB[jj * 3], dy = ay - tB[jj * 3 + 1], dz = az - tB[jj * 3 + 2];
+              const double ed = dscale * sqrt(dx * dx + dy * dy + dz * dz);
+              const double cd = combined_distance_v<FT>(ed, FT != GHICP_FEATURE_NONE ? F[(size_t)j * ks + a] : (fd_t)0, wed, wfd, inv_k);
+              const double c0 = cd - piv;
+              s += c0;
+              s2 += c0 * c0;
+              if (MEMB && cd < pen) { bits |= 1u << (j - j0); cnt++; mx = fmax(mx, -cd); }
+            }
+          }
+          if (MEMB) mask[(size_t)(j0 >> 5) * ks + a] = bits;
+        }
+        if (MEMB) { P.km_cnt[a] = cnt; P.km_lx[a] = mx; }
+      }
+      const double bs = gh_block_sum(s, red);
+      const double bs2 = gh_block_sum(s2, red);
+      if (threadIdx.x == 0) {
+        const size_t b = (size_t)by * rbA + bx;
+        P.psum[b * 2] = bs;
+        P.psum[b * 2 + 1] = bs2;
+      }
+    }
+  }
+  if (MEMB)
+    for (int i = ks + threadIdx.x; i < C.n; i += ROWS) { P.km_cnt[i] = 0u; P.km_lx[i] = -pen; }  // padding rows: all background
+  __syncthreads();
+  dev_penalty(P, red);
+  __syncthreads();
+}
+
+// the count pass of iterations 0 and 1 (and of the feature NONE): dev_km_csr<FT, 0> row by row, and the ballots into the mask
+template <int FT>
+__device__ inline void dev_km_count_mask(const LoopProb& P, const double* sT, unsigned* mask) {
+  typedef typename FdType<FT>::T fd_t;
+  const LoopConst& C = P.C;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double pen = P.st->penalty;
+  const int it = P.st->it;
+  double wfd = 0, wed = 1;
+  if (FT == GHICP_FEATURE_BSC) { wfd = P.wfd[it]; wed = 1.0 - wfd; }
+  const double inv_k = 1.0 / (double)(it + 1);
+  const double* tB = sT ? sT : P.kpT;
+  const fd_t* F = reinterpret_cast<const fd_t*>(P.FD);
+  for (int i = wave; i < C.n; i += 4) {
+    if (i >= C.ks) {  // padding rows: all background
+      if (lane == 0) { P.km_cnt[i] = 0u; P.km_lx[i] = -pen; }
+      continue;
+    }
+    const double sx = P.kpS[(size_t)i * 3], sy = P.kpS[(size_t)i * 3 + 1], sz = P.kpS[(size_t)i * 3 + 2];
+    unsigned c = 0;
+    double mx = -pen;  // km.cpp:56-62 row maximum; every explicit entry is > -penalty
+    for (int j0 = 0; j0 < C.kt; j0 += 64) {
+      const int j = j0 + lane;
+      bool e = false;
+      if (j < C.kt) {
+        const double dx = sx - tB[(size_t)j * 3], dy = sy - tB[(size_t)j * 3 + 1], dz = sz - tB[(size_t)j * 3 + 2];
+        const double ed = (double)C.scale * sqrt(dx * dx + dy * dy + dz * dz);
+        const double cd = combined_distance_v<FT>(ed, FT != GHICP_FEATURE_NONE ? F[(size_t)i * C.kt + j] : (fd_t)0, wed, wfd, inv_k);
+        e = cd < pen;
+        if (e) mx = fmax(mx, -cd);
+      }
+      const unsigned long long b = __ballot(e);
+      if (lane == 0) {
+        mask[(size_t)(j0 >> 5) * C.ks + i] = (unsigned)b;
+        mask[(size_t)((j0 >> 5) + 1) * C.ks + i] = (unsigned)(b >> 32);
+      }
+      c += __popcll(b);
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) { P.km_cnt[i] = c; P.km_lx[i] = mx; }
+  }
+}
+
+// the fill: one wave per row, the row's members from its mask words (the next word is loaded before this one's block is worked on).  A row's
+// entries equal its count by construction; even so nothing is ever stored at or beyond km_rptr[i + 1], and a mismatch is reported in km_status
+// (bit 8: the host fails the call with the solver's status message)
+template <int FT>
+__device__ inline void dev_km_fill_mask(const LoopProb& P, const double* sT, const unsigned* mask) {
+  typedef typename FdType<FT>::T fd_t;
+  const LoopConst& C = P.C;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int it = P.st->it;
+  double wfd = 0, wed = 1;
+  if (FT == GHICP_FEATURE_BSC) { wfd = P.wfd[it]; wed = 1.0 - wfd; }
+  const double inv_k = 1.0 / (double)(it + 1);
+  const double* tB = sT ? sT : P.kpT;
+  const fd_t* F = reinterpret_cast<const fd_t*>(P.FD);
+  int* __restrict__ cols = P.km_cols;
+  double* __restrict__ vals = P.km_vals;
+  const int nw = cdiv_dev(C.kt, 64);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int i = wave; i < C.ks; i += 4) {
+    const double sx = P.kpS[(size_t)i * 3], sy = P.kpS[(size_t)i * 3 + 1], sz = P.kpS[(size_t)i * 3 + 2];
+    const unsigned base = P.km_rptr[i], end = P.km_rptr[i + 1];
+    unsigned c = 0;
+    bool bad = false;
+    unsigned long long b = (unsigned long long)mask[i] | ((unsigned long long)mask[(size_t)C.ks + i] << 32);
+    for (int w = 0; w < nw; w++) {
+      const unsigned long long cur = b;
+      if (w + 1 < nw) b = (unsigned long long)mask[(size_t)(2 * w + 2) * C.ks + i] | ((unsigned long long)mask[(size_t)(2 * w + 3) * C.ks + i] << 32);
+      if (cur == 0ull) continue;
+      const int j = w * 64 + lane;
+      if ((cur >> lane) & 1ull) {
+        const double dx = sx - tB[(size_t)j * 3], dy = sy - tB[(size_t)j * 3 + 1], dz = sz - tB[(size_t)j * 3 + 2];
+        const double ed = (double)C.scale * sqrt(dx * dx + dy * dy + dz * dz);
+        const double cd = combined_distance_v<FT>(ed, FT != GHICP_FEATURE_NONE ? F[(size_t)i * C.kt + j] : (fd_t)0, wed, wfd, inv_k);
+        const unsigned off = base + c + __popcll(cur & below);
+        if (off < end) { cols[off] = j; vals[off] = -cd; }
+        else bad = true;
+      }
+      c += __popcll(cur);
+    }
+    if (bad || c != end - base) atomicOr(P.km_status, 0x100);
+  }
+}
+
+template <int FT, bool MEMB>
+__device__ __noinline__ void pl_graph_km(const LoopProb& P, int* ired, const double* sT, unsigned* mask) {
+  if (!MEMB) dev_km_count_mask<FT>(P, sT, mask);
+  __syncthreads();
+  dev_km_scan_desc(P, ired);
+  __syncthreads();
+  dev_km_fill_mask<FT>(P, sT, mask);
+  __syncthreads();
+}
 template <bool PROF>
 __device__ __noinline__ void pl_km(const Km2Problem* desc, int km_flags, char* smem, int lds_bytes) {
   const Km2Problem KP = *desc;
@@ -619,7 +837,8 @@ template <int FT, bool PROF>
 __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restrict__ probs, const int* __restrict__ order, const int npairs, int* qhead,
                                                   const int km_flags, const int lds_bytes, unsigned long long* lstat, int* progress,
                                                   const int* __restrict__ order2, const int npairs2, int* qhead2,
-                                                  unsigned short* __restrict__ scr, const long long scr_stride) {
+                                                  unsigned short* __restrict__ scr, const long long scr_stride,
+                                                  unsigned* mask_all, const long long mask_stride) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sB = reinterpret_cast<double*>(smem);
   double* red = sB + CHUNK_MAX * 3;
@@ -627,7 +846,7 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
   int* ired = reinterpret_cast<int*>(sh + 32);
   volatile int* s_idx = ired + 18;  // (no static LDS in this kernel: the launch may ask for all 160 KB as dynamic LDS)
   const unsigned long long t_slot0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  unsigned long long t_solve = 0ull, t_solve_max = 0ull, n_solve = 0ull;
+  unsigned long long t_solve = 0ull, t_solve_max = 0ull, n_solve = 0ull, t_sweep = 0ull, t_graph = 0ull, t_tail = 0ull;
   // A slot is one wave's dependent instruction stream for most of its life (the solver's flood and DFS), and in the tail of a batch it
   // shares its SIMD with the throughput kernels of the next batch's front end: behind 7 ALU-bound waves it would get every eighth issue
   // slot.  The heaviest matrices of the 64 bench scenes are the LATE iterations of the slowest pairs -- exactly the tail --, ~240 ms
@@ -654,8 +873,28 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
     unsigned long long t_pair_max = 0ull;
     int it_pair_max = 0;
     while (*(volatile int*)&P.st->done == 0) {
-      pl_sweep<FT>(P, sB, red);   // calED + calCD_* + sums + penalty (ghicp_reg.cpp:114-139, 216-341)
-      pl_graph<FT>(P, ired);      // the sparse graph of findcorrespondenceKM (ghicp_reg.cpp:348-365): count, scan, fill
+      // GHICP_LOOP_FUSE (mask_all: this launch's membership masks, one region per slot; nullptr: the three passes of before).  The fused stages
+      // need whole mask words per column chunk: one chunk, or chunks of CHUNK_MAX columns -- what pick_chunks gives this path.  kpT is staged
+      // behind the stage scratch when the slot's LDS holds it.  (Worked out per iteration: nothing of it lives across the stage calls.)
+      unsigned* const mask = mask_all ? mask_all + (size_t)blockIdx.x * (size_t)mask_stride : (unsigned*)nullptr;
+      const bool fuse = mask != nullptr && (P.C.nchunk_b == 1 || (P.C.chunk_b & 31) == 0);
+      double* const sT = PL_KPT_OFF + (long long)P.C.kt * 24 <= (long long)lds_bytes ? reinterpret_cast<double*>(smem + PL_KPT_OFF) : (double*)nullptr;
+      if (lstat) t_sweep -= __builtin_amdgcn_s_memrealtime();
+      // calED + calCD_* + sums + penalty (ghicp_reg.cpp:114-139, 216-341), then the sparse graph of findcorrespondenceKM
+      // (ghicp_reg.cpp:348-365): count, scan, fill
+      if (!fuse) {
+        pl_sweep<FT>(P, sB, red);
+        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        pl_graph<FT>(P, ired);
+      } else if (FT != GHICP_FEATURE_NONE && *(volatile int*)&P.st->it > 1) {  // the penalty is known before the sweep: membership inside it
+        pl_sweep_km<FT, FT != GHICP_FEATURE_NONE>(P, sB, red, sT, mask);
+        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        pl_graph_km<FT, FT != GHICP_FEATURE_NONE>(P, ired, sT, mask);
+      } else {
+        pl_sweep_km<FT, false>(P, sB, red, sT, mask);
+        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        pl_graph_km<FT, false>(P, ired, sT, mask);
+      }
       const unsigned long long t0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;
       // Km::kmsolve (km.cpp:40-126); the layout per pair from its n (scr: this slot's region of the compact layout's global scratch)
       if (k4_takes_compact(P.C.n, km_flags, lds_bytes))
@@ -664,10 +903,12 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
         pl_km<PROF>(P.km_desc, km_flags, smem, lds_bytes);
       if (lstat) {
         const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t0;
+        t_graph += t0; t_tail -= t0 + dt;
         t_solve += dt; t_solve_max = dt > t_solve_max ? dt : t_solve_max; n_solve++;
         if (dt > t_pair_max) { t_pair_max = dt; it_pair_max = *(volatile int*)&P.st->it; }
       }
       pl_solve<FT>(P, red, ired, sh);  // Km::output, transformestimation, adjustweight (ghicp_reg.cpp:416-460, 605-927)
+      if (lstat) t_tail += __builtin_amdgcn_s_memrealtime();
     }
     if (threadIdx.x == 0 && lstat) {
       P.st->t_end = __builtin_amdgcn_s_memrealtime();
@@ -688,6 +929,9 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
     atomicAdd(&lstat[4], n_solve);
     atomicAdd(&lstat[5], t1 - t_slot0);
     atomicAdd(&lstat[6], 1ull);
+    atomicAdd(&lstat[8], t_sweep);  // the stages around the solve, summed over all pair-iterations of the batch (ghicp_ctx_pair_loop_stats)
+    atomicAdd(&lstat[9], t_graph);
+    atomicAdd(&lstat[10], t_tail);
   }
 }
 
@@ -778,6 +1022,18 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
       GH_TRY(ctx->reserve(B_KM_SLACK, slots * (size_t)scr_stride, &scr));
     }
   }
+  // the membership mask of the fused stages (GHICP_LOOP_FUSE): 2 ceil(n / 64) words of 32 bits per row, one region per solve slot, sized and
+  // handed out like the compact layout's scratch
+  unsigned* msk = nullptr;
+  long long msk_stride = 0;
+  if (ctx->loop_fuse) {
+    int n_all = 1;
+    for (int c = 0; c < nc; c++) n_all = std::max(n_all, plan.nmax[c]);
+    msk_stride = 2ll * cdiv(n_all, 64) * n_all;
+    size_t slots = 0;
+    for (int c = 0; c < nc; c++) slots += 2 * (size_t)std::min(plan.count[c], 4 * ctx->num_cu);
+    GH_TRY(ctx->reserve(B_KM_MASK, slots * (size_t)msk_stride, &msk));
+  }
   GH_HIP(hipMemsetAsync(dqheads, 0, 16 * sizeof(int), s));
   // one launch record per BATCH: the classes of a batch share it (first slot start, last slot end, sums over all slots), and the batch's
   // capacity is what can be resident at once: all its workgroups, but not more than the slots of the roomiest class (the classes compete
@@ -867,13 +1123,14 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
     const int n2 = steal ? plan.count[1] : 0;
     int* q2 = steal ? dqheads + 1 : (int*)nullptr;
     unsigned short* scr_c = scr ? scr + scr_next * (size_t)scr_stride : nullptr;
+    unsigned* msk_c = msk ? msk + scr_next * (size_t)msk_stride : nullptr;
     scr_next += (size_t)grid;
     if (prof)
       hipLaunchKernelGGL((k_pair_loop<FT, true>), dim3(grid), dim3(K4_T), lds, sc, dprobs, (const int*)(plan.d_order + plan.begin[c]), plan.count[c],
-                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride);
+                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride, msk_c, msk_stride);
     else
       hipLaunchKernelGGL((k_pair_loop<FT, false>), dim3(grid), dim3(K4_T), lds, sc, dprobs, (const int*)(plan.d_order + plan.begin[c]), plan.count[c],
-                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride);
+                         dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, o2, n2, q2, scr_c, scr_stride, msk_c, msk_stride);
     ctx->kt_end_on(KT_PAIR_LOOP_DISPATCH, kd, sc);
     GH_HIP_JOIN(hipGetLastError());
     if (c > 0 || confined) {
@@ -883,14 +1140,15 @@ int run_pair_loop(ghicp_ctx* ctx, const LoopProb* dprobs, int nb, const Km4Plan&
     if (confined && c == 1 && !stole) {  // ... and the four-per-CU class once more, on the confined CUs, after the three-per-CU class (only when that class's slots could not take the queue over themselves)
       const int grid2 = std::min(plan.count[c], per_cu * confine_b);
       unsigned short* scr_c2 = scr ? scr + scr_next * (size_t)scr_stride : nullptr;
+      unsigned* msk_c2 = msk ? msk + scr_next * (size_t)msk_stride : nullptr;
       scr_next += (size_t)grid2;
       hipEvent_t kd2 = ctx->kt_begin_on(KT_PAIR_LOOP_DISPATCH, ctx->confine_stream);
       if (prof)
         hipLaunchKernelGGL((k_pair_loop<FT, true>), dim3(grid2), dim3(K4_T), lds, ctx->confine_stream, dprobs, (const int*)(plan.d_order + plan.begin[c]),
-                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride);
+                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride, msk_c2, msk_stride);
       else
         hipLaunchKernelGGL((k_pair_loop<FT, false>), dim3(grid2), dim3(K4_T), lds, ctx->confine_stream, dprobs, (const int*)(plan.d_order + plan.begin[c]),
-                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride);
+                           plan.count[c], dqheads + c, kflags, (int)lds, lstat, ctx->progress_host, (const int*)nullptr, 0, (int*)nullptr, scr_c2, scr_stride, msk_c2, msk_stride);
       ctx->kt_end_on(KT_PAIR_LOOP_DISPATCH, kd2, ctx->confine_stream);
       GH_HIP_JOIN(hipGetLastError());
       batch_grid += grid2;

@@ -99,9 +99,11 @@ int ghicp_ctx_kernel_time(ghicp_ctx* ctx, const char* name, double* total_ms, in
 int ghicp_ctx_km_launch_stats(ghicp_ctx* ctx, double* out8);
 /* Records of the persistent pair loop (Kuhn-Munkres configurations of ghicp_register_pairs / ghicp_register_clouds: one workgroup =
  * one solve slot runs a pair's whole ghicp_reg loop, src/ghicp_reg.cpp:49-103, and then pops the next pair), collected while kernel
- * timing is on: out8 = { batches, workgroups that ran, solves, mean solve ms, longest solve ms, mean batch span ms, idle-slot fraction
- * (1 - slot lifetimes / (resident slots x span): the tail of a batch), share of the slot lifetimes spent inside Kuhn-Munkres solves }. */
-int ghicp_ctx_pair_loop_stats(ghicp_ctx* ctx, double* out8);
+ * timing is on: out12 = { batches, workgroups that ran, solves, mean solve ms, longest solve ms, mean batch span ms, idle-slot fraction
+ * (1 - slot lifetimes / (resident slots x span): the tail of a batch), share of the slot lifetimes spent inside Kuhn-Munkres solves,
+ * mean ms per pair-iteration in the statistics sweep, in the graph build, in the tail after the solve, 0 }.  (TWELVE doubles: the stage
+ * times were appended to the eight of earlier versions.) */
+int ghicp_ctx_pair_loop_stats(ghicp_ctx* ctx, double* out12);
 /* Diagnostics: Kuhn-Munkres solves of this context's batched loops (ghicp_register_pairs / ghicp_register_clouds, Ct = KM) that went through the
  * solver's literal single-lane fallback since the context was created (rule R4's hazard check, km4_dev.h: correct, slow by design;
  * expected 0 on finite inputs -- a non-zero count explains multi-second solves). */
