@@ -48,7 +48,7 @@ class PairStats(C.Structure):
 EXPORTS = [
     "ghicp_ctx_create", "ghicp_ctx_destroy", "ghicp_ctx_set_stream", "ghicp_ctx_set_host_pointers", "ghicp_ctx_stage_stats", "ghicp_ctx_stage_clear", "ghicp_ctx_set_cu_mask",
     "ghicp_ctx_synchronize", "ghicp_ctx_kernel_timing", "ghicp_ctx_kernel_time", "ghicp_ctx_km_launch_stats", "ghicp_ctx_pair_loop_stats", "ghicp_ctx_loop_timeline", "ghicp_ctx_set_loop_cost_hints", "ghicp_ctx_loop_progress", "ghicp_ctx_loop_progress_reset", "ghicp_ctx_loop_hazards", "ghicp_last_error", "ghicp_version", "ghicp_params_default",
-    "ghicp_voxel_filter", "ghicp_sort_pairs", "ghicp_scan_inclusive_u32", "ghicp_select_flagged", "ghicp_unique_sorted_u32", "ghicp_gather_points", "ghicp_bbx_magnitude", "ghicp_cloud_bounds", "ghicp_pca_curvature", "ghicp_prune",
+    "ghicp_voxel_filter", "ghicp_knn_mean_distance", "ghicp_sor_filter", "ghicp_dis_filter", "ghicp_box_filter", "ghicp_sort_pairs", "ghicp_scan_inclusive_u32", "ghicp_select_flagged", "ghicp_unique_sorted_u32", "ghicp_gather_points", "ghicp_bbx_magnitude", "ghicp_cloud_bounds", "ghicp_pca_curvature", "ghicp_prune",
     "ghicp_nms", "ghicp_keypoints", "ghicp_keypoints_adaptive", "ghicp_bsc_encode", "ghicp_fpfh", "ghicp_fpfh_keypoints", "ghicp_fd_bsc", "ghicp_fd_fpfh", "ghicp_km_solve",
     "ghicp_rigid_svd", "ghicp_rigid_svd_host", "ghicp_register", "ghicp_loop_create", "ghicp_iterate", "ghicp_loop_result", "ghicp_loop_destroy", "ghicp_transform_cloud", "ghicp_transform_clouds", "ghicp_register_pair",
     "ghicp_register_pairs",
@@ -386,6 +386,50 @@ class Context:
         keep = t.empty(n + 1, dtype=t.int32, device=self.dev)
         m = C.c_int64(0)
         self._check(self.lib.ghicp_voxel_filter(self.h, _ptr(x), C.c_int64(n), x.shape[1], C.c_float(voxel), _ptr(keep), C.byref(m)))
+        return keep[: m.value]
+
+    def knn_mean_distance(self, xyz, mean_k):
+        """the per-point stage of sor_filter: mean distance to the mean_k nearest neighbours (query excluded), (n,) f32 tensor"""
+        t = self.torch
+        x = self._xyz(xyz)
+        out = t.empty(x.shape[0], dtype=t.float32, device=self.dev)
+        self._check(self.lib.ghicp_knn_mean_distance(self.h, _ptr(x), C.c_int64(x.shape[0]), x.shape[1], int(mean_k), _ptr(out)))
+        return out
+
+    def sor_filter(self, xyz, mean_k=50, std_mul=2.0):
+        """CFilter::SORFilter (pcl::StatisticalOutlierRemoval): (kept indices, ascending, int32 tensor; stats = (mean, stddev, threshold,
+        valid count) f64 array).  Fewer than mean_k + 1 points: everything is kept and the stats are NaN, NaN, NaN, 0."""
+        t = self.torch
+        x = self._xyz(xyz)
+        n = x.shape[0]
+        keep = t.empty(max(n, 1), dtype=t.int32, device=self.dev)
+        m = C.c_int64(0)
+        st = (C.c_double * 4)()
+        self._check(self.lib.ghicp_sor_filter(self.h, _ptr(x), C.c_int64(n), x.shape[1], int(mean_k), C.c_double(std_mul), _ptr(keep), C.byref(m), st))
+        return keep[: m.value], np.array(st[:], np.float64)
+
+    def dis_filter(self, xyz, xy_dis_max, z_min, z_max):
+        """CFilter::DisFilter as written (x*x + y + y < xy_dis_max^2, z_min < z < z_max): the kept indices, ascending"""
+        t = self.torch
+        x = self._xyz(xyz)
+        n = x.shape[0]
+        keep = t.empty(max(n, 1), dtype=t.int32, device=self.dev)
+        m = C.c_int64(0)
+        self._check(self.lib.ghicp_dis_filter(self.h, _ptr(x), C.c_int64(n), x.shape[1], C.c_double(xy_dis_max), C.c_double(z_min), C.c_double(z_max),
+                                              _ptr(keep), C.byref(m)))
+        return keep[: m.value]
+
+    def box_filter(self, xyz, boxes):
+        """CFilter::ActiveObjectFilter: boxes (b, 6) = (min_x, min_y, min_z, max_x, max_y, max_z); the indices of the points strictly inside
+        no box, ascending"""
+        t = self.torch
+        x = self._xyz(xyz)
+        n = x.shape[0]
+        b = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 6))
+        keep = t.empty(max(n, 1), dtype=t.int32, device=self.dev)
+        m = C.c_int64(0)
+        self._check(self.lib.ghicp_box_filter(self.h, _ptr(x), C.c_int64(n), x.shape[1], b.ctypes.data_as(C.POINTER(C.c_double)), C.c_int32(b.shape[0]),
+                                              _ptr(keep), C.byref(m)))
         return keep[: m.value]
 
     def sort_pairs(self, keys, vals=None, bit_begin=0, bit_end=None, keys_out=None, vals_out=None):

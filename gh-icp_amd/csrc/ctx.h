@@ -82,6 +82,8 @@ enum BufSlot {
   B_ICP_PEND, B_ICP_TNRM, B_ICP_OUT,
   // generalized ICP (icp.hip): covariances of both clouds, per-correspondence Mahalanobis matrices, the packed source
   B_GICP_COVS, B_GICP_COVT, B_GICP_MAHAL, B_GICP_SRC4,
+  // cleaning filters (filter.hip): mean neighbour distances, their tile sums (also the boxes of the box filter)
+  B_SOR_DIST, B_SOR_PART,
   B_NUM
 };
 

@@ -137,6 +137,30 @@ void ghicp_params_default(ghicp_params* p);
 /* CFilter::voxelfilter (include/filter.hpp:28-88, incl. its phantom-entry quirk: output row 0 is
  * a copy of input point 0).  keep_idx: capacity n+1 int32; *m [host]. */
 int ghicp_voxel_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, float voxel, int32_t* keep_idx, int64_t* m);
+/* CFilter::SORFilter (include/filter.hpp:90-102) = pcl::StatisticalOutlierRemoval::applyFilterIndices as recalled (PCL 1.7 / 1.8; not
+ * checked against its sources -- this comment and DESIGN.md N9 are the one place to correct it).  mean_k in 1..63 (the query and its
+ * neighbours fill the 64 lanes of one wavefront); anything else is GHICP_ERR_ARG.  Finite coordinates are a precondition.
+ *   per point    the mean_k + 1 nearest neighbours in the same cloud, query included; float squared L2 (d2 = dx*dx; d2 += dy*dy;
+ *                d2 += dz*dz, no contraction); the list sorted by d2, entry 0 dropped, sqrtf(d2[t]) summed for t = 1 .. mean_k in
+ *                ascending order in f64, divided by mean_k, rounded to float.  Only the multiset of the mean_k + 1 smallest d2 matters.
+ *   statistics   sum and sq_sum of the float distances in f64 -- tiles of 1024 consecutive indices added in index order, then the tiles
+ *                in index order (N9) --, mean = sum / n, variance = (sq_sum - sum*sum/n) / (n - 1), threshold = mean + std_mul * sqrt(variance)
+ *   kept         point i stays iff !(dist[i] > threshold), the float promoted to f64; input order is kept
+ *   n < mean_k + 1   PCL gets short result lists: every distance is 0, no point is valid, the threshold is NaN and every point stays
+ *                (m = n, stats4 = NaN, NaN, NaN, 0)
+ * ghicp_knn_mean_distance is the per-point stage alone: dist, n floats. */
+int ghicp_knn_mean_distance(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, int mean_k, float* dist);
+/* keep_idx: capacity n int32, the kept points' indices, ascending; *m [host]; stats4 [host] (may be NULL) = mean, stddev, threshold, valid count. */
+int ghicp_sor_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, int mean_k, double std_mul, int32_t* keep_idx, int64_t* m,
+                     double* stats4);
+/* CFilter::DisFilter (include/filter.hpp:105-117) as written (quirk Q10): point i stays iff (double)(float)(x*x + y + y) < xy_dis_max^2 &&
+ * z < z_max && z > z_min -- `+ y + y`, not `+ y*y`.  keep_idx: capacity n, ascending; *m [host]. */
+int ghicp_dis_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, double xy_dis_max, double z_min, double z_max, int32_t* keep_idx,
+                     int64_t* m);
+/* CFilter::ActiveObjectFilter (include/filter.hpp:119-140): a point STRICTLY inside any box leaves (float coordinates against the f64
+ * bounds; a point on a face stays, Q11).  boxes6 [host] = n_boxes x (min_x, min_y, min_z, max_x, max_y, max_z); n_boxes = 0 keeps every point. */
+int ghicp_box_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, const double* boxes6, int32_t n_boxes, int32_t* keep_idx,
+                     int64_t* m);
 /* The stable sort behind the voxel filter, the grids and the NMS order (the reference's std::sort calls, include/filter.hpp:66 and
  * include/keypoint_detect.hpp:119-130, made deterministic: equal keys keep their input order).  Ascending on the key bits
  * [bit_begin, bit_end) of n keys of key_bytes (4 or 8) bytes each; vals_in / vals_out (u32) may both be NULL (keys only).  The inputs are
