@@ -55,7 +55,7 @@ EXPORTS = [
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
     "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
-    "ghicp_register_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
+    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
     "ghicp_pairqueue_barrier", "ghicp_pairqueue_static_share", "ghicp_pairqueue_claim", "ghicp_pairqueue_counter_reset",
     "ghicp_pairqueue_gather_records", "ghicp_pairqueue_pack_records", "ghicp_pairqueue_register_pairs",
@@ -113,6 +113,11 @@ class IcpStats(C.Structure):
     _fields_ = [("done", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("reason", C.c_int32),
                 ("correspondences", C.c_int64), ("overlap", C.c_float), ("pad_", C.c_float),
                 ("mse", C.c_double), ("fitness", C.c_double)]
+
+
+class RefineResult(C.Structure):
+    """ghicp_refine_result: one pair of ghicp_refine_clouds."""
+    _fields_ = [("T_icp", C.c_float * 16), ("Rt_refined", C.c_double * 16), ("stats", IcpStats)]
 
 
 def icp_params(max_iter=50, reciprocal=False, trimmed=False, metric=ICP_POINT_TO_POINT, thre_dis=0.5, min_overlap=0.1,
@@ -736,6 +741,12 @@ class Cloud:
         self.ctx._check(self.ctx.lib.ghicp_cloud_recompute(self.h, _ptr(x), C.c_int64(x.shape[0]), x.shape[1]))
         return self
 
+    def prepare_refine(self, k=0):
+        """What the cloud needs to serve as a target of Context.refine_clouds: its 1-NN grids and, for k in 1..20, its k-NN normals
+        (point-to-plane).  Needed again after every recompute."""
+        self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_refine(self.h, int(k)))
+        return self
+
     def close(self):
         if self.h:
             self.ctx.lib.ghicp_cloud_destroy(self.h)
@@ -793,7 +804,31 @@ def _clouds_recompute(self, clouds, xyzs):
     return clouds
 
 
+def _refine_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
+    """ghicp_refine_clouds: fine ICP of the down-sampled clouds of every (Cloud S, Cloud T) from Rt_init (n x 4 x 4 f64, e.g. the Rt of
+    register_clouds; None: identity) in one launch sequence per iteration.  Targets must have been through Cloud.prepare_refine.
+    Returns per pair the dict of Context.icp (without the transformed cloud) plus Rt_refined (4,4) f64."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    HS = (C.c_void_p * n)(*[a.h.value for a, _ in pairs])
+    HT = (C.c_void_p * n)(*[b.h.value for _, b in pairs])
+    init = None
+    if Rt_init is not None:
+        init = np.ascontiguousarray(Rt_init, dtype=np.float64).reshape(n, 16)
+    res = (RefineResult * n)()
+    self._check(self.lib.ghicp_refine_clouds(self.h, C.byref(params), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
+                                             int(max_concurrent), res))
+    out = []
+    for r in res:
+        d = {k: getattr(r.stats, k) for k, _ in IcpStats._fields_ if k != "pad_"}
+        d.update(T=np.array(r.T_icp[:], np.float32).reshape(4, 4), Rt_refined=np.array(r.Rt_refined[:], np.float64).reshape(4, 4))
+        out.append(d)
+    return out
+
+
 Context.cloud_create = _cloud_create
+Context.refine_clouds = _refine_clouds
 Context.clouds_recompute = _clouds_recompute
 Context.cloud_from_features = _cloud_from_features
 Context.register_clouds = _register_clouds

@@ -662,6 +662,7 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   for (int b = 0; b < nb; b++) {
     ghicp_cloud* c = clouds[b];
     c->n = n[b]; c->m = 0; c->k = 0; c->cand = 0; c->bbx = 0.f;
+    c->rf_invalidate();
     c->V = cfg.reg.dof > 4 ? 4 : (cfg.reg.dof > 0 ? 2 : 1);
     H->c[b].xyz = xyz[b]; H->c[b].n = (int)n[b]; H->c[b].stride = stride;
     H->roff[b + 1] = H->roff[b] + (int)n[b];

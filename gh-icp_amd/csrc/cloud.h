@@ -1,6 +1,6 @@
 // Internal: the per-cloud front-end cache handle (cloud.hip) -- shared with the batched front end (batch.hip).
 #pragma once
-#include "ctx.h"
+#include "grid.h"
 
 struct ghicp_cloud {
   ghicp_ctx* ctx = nullptr;
@@ -12,6 +12,14 @@ struct ghicp_cloud {
   DevBuf kp;    // k int32: keypoint ids into ds
   DevBuf kpx;   // k x 3 f64
   DevBuf feat;  // BSC: 4 x k x 56 bytes (variants 0..V-1 filled) | FPFH: k x 33 f32 | None: empty
+  // what the cloud needs to serve as the TARGET of the batched fine registration (ghicp_cloud_prepare_refine, refine.hip): the fine and
+  // coarse 1-NN grids over ds, and the k-NN normals of ds for k = rf_k (0: none).  Invalid after every recompute.
+  bool rf_ready = false;
+  int rf_k = 0;
+  GridDesc rf_fine, rf_coarse;
+  DevBuf rf_fpts, rf_fstart, rf_cpts, rf_cstart, rf_nrm;
+  void rf_invalidate() { rf_ready = false; rf_k = 0; }
+  void rf_release() { rf_invalidate(); rf_fpts.release(); rf_fstart.release(); rf_cpts.release(); rf_cstart.release(); rf_nrm.release(); }
 };
 
 inline bool same_front_end(const ghicp_pair_config& a, const ghicp_pair_config& b) {

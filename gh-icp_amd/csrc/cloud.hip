@@ -46,6 +46,7 @@ static int cloud_fill(ghicp_ctx* ctx, ghicp_cloud* c, const float* d, long long 
   hipStream_t s = ctx->stream;
   const ghicp_pair_config* cfg = &c->cfg;
   c->n = n; c->m = 0; c->k = 0; c->cand = 0;
+  c->rf_invalidate();
   c->V = cfg->reg.dof > 4 ? 4 : (cfg->reg.dof > 0 ? 2 : 1);
   // down-sampling (main:89-90)
   if (cfg->voxel > 0.f) {
@@ -151,6 +152,7 @@ extern "C" int ghicp_cloud_destroy(ghicp_cloud* c) {
   if (!c) return GHICP_OK;
   if (c->ctx) (void)hipSetDevice(c->ctx->device);
   c->ds.release(); c->kp.release(); c->kpx.release(); c->feat.release();
+  c->rf_release();
   delete c;
   return GHICP_OK;
 }

@@ -1,0 +1,544 @@
+// Internal: what the single-pair fine registration (icp.hip) and its batched form over cached clouds (refine.hip) share -- the
+// search grids, the per-pair loop state, and the bodies of the per-iteration kernels.  A body takes the block index within ITS pair
+// (and, where a kernel strides over the points, the number of blocks of that pair), so that a batched launch gives every pair the
+// block shape, the partial records and the reduction order of the single-pair launch: same sums, bit for bit.
+#pragma once
+#include "grid.h"
+#include "devmath.h"
+
+#include <cmath>
+#include <cstdlib>
+
+namespace icpdev {
+
+constexpr float kInf = 3.0e38f;
+constexpr int RCAP = 2;     // rings searched per query on the fine grid before it is handed to the coarse grid
+constexpr int NBLK = 512;   // partial-sum blocks of the accumulation kernels
+constexpr int NPART = 32;   // doubles per partial record
+
+struct NnGrid {
+  GridDesc d;
+  const float4* pts;
+  const unsigned* start;
+  float cell;
+};
+
+struct NnIndex {
+  NnGrid fine, coarse;
+};
+
+struct IcpState {
+  float T[16];    // transformation_ of this iteration
+  float fin[16];  // final_transformation_
+  double prev_mse, mse, eps_t, eps_e;
+  float msf[3], mtf[3];
+  int iterations, max_iter, converged, reason;
+  unsigned count, nv;  // valid correspondences / kept after trimming
+  int trimmed, metric;
+  float ratio;
+  unsigned pend;
+  // radix select of the trimming threshold K* = (d2star, istar): correspondences with a smaller (d2 bits, index) are kept
+  unsigned sel_prefix[6], sel_rank[6];
+  unsigned d2star, istar;
+  int sel_done;
+  // batched loop (refine.hip) only: a pair the overlap gate refused (or an empty one) never runs; the sum behind getFitnessScore()
+  int refused;
+  double fit_sum;
+};
+
+// A pair of a batch that has left its loop -- converged, stopped without correspondences, or refused -- is FROZEN: the single-pair loop
+// stops launching for it, so no block of a batched launch may touch its points, its state or its partial records again.
+__device__ inline bool icp_frozen(const IcpState* st) { return st->refused || st->converged || st->reason == GHICP_ICP_NO_CORRESPONDENCES; }
+
+// ------------------------------------------------------------------------------------------------ 1-NN search
+// Rounding margin of axis a: how far beyond the face mn + k * cell a point assigned to cell k may lie.  The cell of a point
+// is floor((v - mn) * inv), three float roundings plus that of cell = 1 / inv: an error of up to 2.4e-7 * k cells at cell
+// k, so the margin grows with the cells of the axis (a 0.02 m cell along a line of 400 m is 20 000 cells) on top of a
+// flat 2e-3 cell.  The rounding of mn + k * cell itself is monotone and cannot put a float on the wrong side of a face.
+__device__ inline float axis_margin(const NnGrid& G, int a) { return (2e-3f + 4e-7f * (float)G.d.dim[a]) * G.cell; }
+
+// Lower bound on the distance from p to any point in a cell outside the block [c - r, c + r]^3 (sides clipped by the
+// grid need no bound: nothing lies beyond them).  The margin is SUBTRACTED: a point of a cell outside the block may lie
+// that far inside the block's faces.
+__device__ inline float block_reach(const NnGrid& G, float px, float py, float pz, int cx, int cy, int cz, int r) {
+  float m = kInf;
+  const float p[3] = {px, py, pz};
+  const int c[3] = {cx, cy, cz};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float mg = axis_margin(G, a);
+    if (c[a] - r > 0) m = fminf(m, p[a] - (G.d.mn[a] + (float)(c[a] - r) * G.cell) - mg);
+    if (c[a] + r < G.d.dim[a] - 1) m = fminf(m, (G.d.mn[a] + (float)(c[a] + r + 1) * G.cell) - p[a] - mg);
+  }
+  return m;
+}
+
+// Lower bound on the squared distance from coordinate p to any point the grid assigns to the cells [lo, hi] of one axis.
+// Callers skip a run when this exceeds the best distance so far, so it must never over-estimate: the interval is WIDENED
+// by the margin on both sides (a point on a cell face, or a hair beyond it, may be assigned to either neighbour; when
+// every target sits on a face -- a line or a thin bar along an axis has y = z = mn -- that decides which runs are read).
+__device__ inline float axis_gap2(const NnGrid& G, int a, float p, int lo, int hi) {
+  const float m = axis_margin(G, a);
+  const float l = G.d.mn[a] + (float)lo * G.cell - m, h = G.d.mn[a] + (float)(hi + 1) * G.cell + m;
+  const float d = fmaxf(fmaxf(l - p, p - h), 0.f);
+  return d * d;
+}
+
+// The cells of block r that are not in block rlo (rlo = -1: the whole block), as z-contiguous runs of the point array.
+// bound(x) is called before every x slab and returns the squared distance beyond which a run cannot matter; runs whose
+// box lies farther than that from P are skipped (a point at exactly the bound still ties, hence the strict test).
+template <typename B, typename F>
+__device__ inline void for_shell_runs(const NnGrid& G, float px, float py, float pz, int cx, int cy, int cz, int rlo, int r, B&& bound, F&& f) {
+  const GridDesc& g = G.d;
+  const unsigned* __restrict__ start = G.start;
+  const int x0 = max(cx - r, 0), x1 = min(cx + r, g.dim[0] - 1);
+  const int y0 = max(cy - r, 0), y1 = min(cy + r, g.dim[1] - 1);
+  const int zl = max(cz - r, 0), zh = min(cz + r, g.dim[2] - 1);
+  for (int x = x0; x <= x1; x++) {
+    const float lim = bound(x);
+    const float gx = axis_gap2(G, 0, px, x, x);
+    if (gx > lim) continue;
+    for (int y = y0; y <= y1; y++) {
+      const float gxy = gx + axis_gap2(G, 1, py, y, y);
+      if (gxy > lim) continue;
+      const unsigned base = ((unsigned)x * g.dim[1] + y) * g.dim[2];
+      if (max(abs(x - cx), abs(y - cy)) > rlo) {
+        if (gxy + axis_gap2(G, 2, pz, zl, zh) > lim) continue;
+        const unsigned b = start[base + zl], e = start[base + zh + 1];
+        if (e > b) f(b, e);
+      } else {
+        const int a1 = min(cz - rlo - 1, g.dim[2] - 1);
+        if (zl <= a1 && !(gxy + axis_gap2(G, 2, pz, zl, a1) > lim)) {
+          const unsigned b = start[base + zl], e = start[base + a1 + 1];
+          if (e > b) f(b, e);
+        }
+        const int b0 = max(cz + rlo + 1, 0);
+        if (b0 <= zh && !(gxy + axis_gap2(G, 2, pz, b0, zh) > lim)) {
+          const unsigned b = start[base + b0], e = start[base + zh + 1];
+          if (e > b) f(b, e);
+        }
+      }
+    }
+  }
+}
+
+__device__ inline void nn_fine_body(const NnGrid& G, const float4* __restrict__ q, int nq, int i, int* __restrict__ nn, float* __restrict__ nd,
+                                    unsigned* __restrict__ pend_list, unsigned* __restrict__ pend_count) {
+  if (i >= nq) return;
+  const float4 P = q[i];
+  const int cx = gh_cell_coord(P.x, G.d.mn[0], G.d.inv, G.d.dim[0]);
+  const int cy = gh_cell_coord(P.y, G.d.mn[1], G.d.inv, G.d.dim[1]);
+  const int cz = gh_cell_coord(P.z, G.d.mn[2], G.d.inv, G.d.dim[2]);
+  float bd = kInf;
+  int bi = -1;
+  bool done = false;
+  int rlo = -1;
+  for (int r = 1; r <= RCAP; r++) {
+    for_shell_runs(G, P.x, P.y, P.z, cx, cy, cz, rlo, r, [&](int) { return bd; }, [&](unsigned b, unsigned e) {
+      for (unsigned t = b; t < e; t++) {
+        const float4 Q = G.pts[t];
+        const int qi = (int)__float_as_uint(Q.w);
+        const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+        float d2 = dx * dx;
+        d2 += dy * dy;
+        d2 += dz * dz;
+        if (d2 < bd || (d2 == bd && qi < bi)) { bd = d2; bi = qi; }
+      }
+    });
+    rlo = r;
+    const float reach = block_reach(G, P.x, P.y, P.z, cx, cy, cz, r);
+    if (reach >= kInf || (reach > 0.f && bd < reach * reach)) { done = true; break; }
+  }
+  nn[i] = bi;
+  nd[i] = bd;
+  if (!done) pend_list[atomicAdd(pend_count, 1u)] = (unsigned)i;
+}
+
+__device__ inline unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// One wave per unresolved query, seeded with the fine-grid candidate; ring expansion without a cap.
+__device__ inline void nn_coarse_body(const NnGrid& G, const float4* __restrict__ q, const unsigned* __restrict__ pend_list, unsigned np, unsigned w0,
+                                      unsigned nw, int* __restrict__ nn, float* __restrict__ nd) {
+  const int lane = threadIdx.x & 63;
+  for (unsigned w = w0; w < np; w += nw) {
+    const unsigned i = pend_list[w];
+    const float4 P = q[i];
+    const int cx = gh_cell_coord(P.x, G.d.mn[0], G.d.inv, G.d.dim[0]);
+    const int cy = gh_cell_coord(P.y, G.d.mn[1], G.d.inv, G.d.dim[1]);
+    const int cz = gh_cell_coord(P.z, G.d.mn[2], G.d.inv, G.d.dim[2]);
+    unsigned long long best = ((unsigned long long)__float_as_uint(nd[i]) << 32) | (unsigned)nn[i];
+    for (int r = 0;; r++) {
+      // Shell r as 2 slots per (x, y) column of the block: a rim column is one z run (slot 0), an interior column its two
+      // cap cells.  The lanes look the slots up in parallel (box test against the wave's best, then the cell table), then
+      // the wave walks the non-empty runs together: no serial chain of table lookups per column.
+      const int side = 2 * r + 1, slots = 2 * side * side;
+      for (int s0 = 0; s0 < slots; s0 += 64) {
+        best = wave_min_u64(best);
+        const float lim = __uint_as_float((unsigned)(best >> 32));
+        unsigned rb = 0, re = 0;
+        const int sl = s0 + lane;
+        if (sl < slots) {
+          const int c = sl >> 1, h = sl & 1;
+          const int x = cx + c / side - r, y = cy + c % side - r;
+          if (x >= 0 && x < G.d.dim[0] && y >= 0 && y < G.d.dim[1]) {
+            const bool rim = max(abs(x - cx), abs(y - cy)) == r;
+            int zl, zh;
+            if (rim) { zl = cz - r; zh = h ? zl - 1 : cz + r; }
+            else { zl = zh = h ? cz + r : cz - r; }
+            if (r == 0 && h) zh = zl - 1;
+            zl = max(zl, 0); zh = min(zh, G.d.dim[2] - 1);
+            if (zl <= zh && !(axis_gap2(G, 0, P.x, x, x) + axis_gap2(G, 1, P.y, y, y) + axis_gap2(G, 2, P.z, zl, zh) > lim)) {
+              const unsigned base = ((unsigned)x * G.d.dim[1] + y) * G.d.dim[2];
+              rb = G.start[base + zl];
+              re = G.start[base + zh + 1];
+            }
+          }
+        }
+        unsigned long long live = __ballot(re > rb);
+        while (live) {
+          const int l = __ffsll((long long)live) - 1;
+          live &= live - 1;
+          const unsigned b = __shfl(rb, l, 64), e = __shfl(re, l, 64);
+          for (unsigned t = b + lane; t < e; t += 64) {
+            const float4 Q = G.pts[t];
+            const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+            float d2 = dx * dx;
+            d2 += dy * dy;
+            d2 += dz * dz;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(Q.w);
+            best = key < best ? key : best;
+          }
+        }
+      }
+      best = wave_min_u64(best);
+      const float bd = __uint_as_float((unsigned)(best >> 32));
+      const float reach = block_reach(G, P.x, P.y, P.z, cx, cy, cz, r);
+      if (reach >= kInf || (reach > 0.f && bd < reach * reach)) break;
+    }
+    if (lane == 0) {
+      nn[i] = (int)(unsigned)best;
+      nd[i] = __uint_as_float((unsigned)(best >> 32));
+    }
+  }
+}
+
+// adds the number of threads of a 256-thread block with `flag` set to *dst: one atomic per block
+__device__ inline void block_count_add(bool flag, unsigned* dst) {
+  __shared__ unsigned wsum[4];
+  const unsigned long long b = __ballot(flag);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (t) atomicAdd(dst, t);
+  }
+}
+
+// CorrespondenceRejectorTrimmed::getRemainingCorrespondences: floor(overlap_ratio * float(size))
+__device__ inline void icp_prep_body(IcpState* st) {
+  unsigned nv = st->count;
+  if (st->trimmed) {
+    const unsigned t = (unsigned)(int)floorf(st->ratio * (float)st->count);
+    if (t < nv) nv = t;
+  }
+  st->nv = nv;
+  st->sel_prefix[0] = 0;
+  st->sel_rank[0] = nv;
+  st->sel_done = nv >= st->count;  // nothing to trim: every valid correspondence is kept
+  st->d2star = 0xffffffffu;
+  st->istar = 0xffffffffu;
+}
+
+// ---- trimmed rejector without a sort.  The kept set is {key < K*} with key = (d2 bits, source index) and K* the key of
+// rank nv: an MSD radix select, three digit passes (11 + 11 + 10 bits) over the distance bits, then -- only when ties at
+// the threshold distance have to be split -- three over the index bits.  Every pass is one histogram kernel whose blocks
+// first derive the prefix chosen so far from the previous pass's histogram.
+constexpr int SEL_BINS = 2048;
+__device__ inline int sel_bits(int p) { return (p % 3 == 2) ? 10 : 11; }
+__device__ inline int sel_shift(int p) { return (p % 3 == 0) ? 21 : ((p % 3 == 1) ? 10 : 0); }
+
+// bin of `hist` (SEL_BINS entries) that holds rank r; *below = entries in lower bins.  Block-cooperative, 256 threads.
+__device__ inline unsigned sel_pick(const unsigned* __restrict__ hist, unsigned r, unsigned* below, int* scan_s, unsigned* pick_s) {
+  unsigned c[8], sum = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { c[k] = hist[threadIdx.x * 8 + k]; sum += c[k]; }
+  int tot;
+  const unsigned ex = (unsigned)gh_block_excl_scan((int)sum, scan_s, &tot);
+  if (r >= ex && r < ex + sum) {
+    unsigned acc = ex;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      if (r >= acc && r < acc + c[k]) { pick_s[0] = threadIdx.x * 8 + k; pick_s[1] = acc; }
+      acc += c[k];
+    }
+  }
+  __syncthreads();
+  *below = pick_s[1];
+  return pick_s[0];
+}
+
+__device__ inline void sel_pass_body(int pass, const int* __restrict__ nn, const float* __restrict__ nd, int n, IcpState* __restrict__ st,
+                                     unsigned* __restrict__ hist, unsigned blk, unsigned nblk) {
+  if (st->sel_done || (pass > 3 && st->istar == 0)) return;
+  __shared__ unsigned lh[SEL_BINS];
+  __shared__ int scan_s[20];
+  __shared__ unsigned pick_s[2];
+  unsigned prefix = 0, rank = st->sel_rank[0], d2star = st->d2star;
+  if (pass > 0) {
+    unsigned below;
+    const unsigned bin = sel_pick(hist + (size_t)(pass - 1) * SEL_BINS, st->sel_rank[pass - 1], &below, scan_s, pick_s);
+    prefix = (st->sel_prefix[pass - 1] << sel_bits(pass - 1)) | bin;
+    rank = st->sel_rank[pass - 1] - below;
+    if (pass == 3) {  // the distance is fixed: `rank` of its ties (lowest indices first) are kept
+      d2star = prefix;
+      prefix = 0;
+      if (blk == 0 && threadIdx.x == 0) {
+        st->d2star = d2star;
+        if (rank == 0) st->istar = 0;
+      }
+      if (rank == 0) return;  // K* is the first tie: no index digits needed (k_sel_final sees rank 0 too)
+    }
+    if (blk == 0 && threadIdx.x == 0) { st->sel_prefix[pass] = prefix; st->sel_rank[pass] = rank; }
+  }
+  for (int k = threadIdx.x; k < SEL_BINS; k += 256) lh[k] = 0;
+  __syncthreads();
+  const int shift = sel_shift(pass), bits = sel_bits(pass);
+  for (int i = blk * 256 + threadIdx.x; i < n; i += nblk * 256) {
+    if (nn[i] < 0) continue;
+    const unsigned db = __float_as_uint(nd[i]);
+    unsigned v;
+    bool member;
+    if (pass < 3) { v = db; member = pass == 0 || (v >> (shift + bits)) == prefix; }
+    else { v = (unsigned)i; member = db == d2star && (pass == 3 || (v >> (shift + bits)) == prefix); }
+    if (member) atomicAdd(&lh[(v >> shift) & ((1u << bits) - 1u)], 1u);
+  }
+  __syncthreads();
+  unsigned* out = hist + (size_t)pass * SEL_BINS;
+  for (int k = threadIdx.x; k < SEL_BINS; k += 256)
+    if (lh[k]) atomicAdd(&out[k], lh[k]);
+}
+
+__device__ inline void sel_final_body(IcpState* __restrict__ st, const unsigned* __restrict__ hist) {
+  if (st->sel_done) return;
+  __shared__ int scan_s[20];
+  __shared__ unsigned pick_s[2];
+  if (st->istar == 0) return;  // decided at pass 3
+  unsigned below;
+  const unsigned bin = sel_pick(hist + (size_t)5 * SEL_BINS, st->sel_rank[5], &below, scan_s, pick_s);
+  if (threadIdx.x == 0) st->istar = (st->sel_prefix[5] << 10) | bin;
+}
+
+struct CorrView {
+  const int* nn;
+  const float* nd;
+  const float4* cur;
+  const float4* tgt;
+  int ns;
+};
+
+// source point e -> its target j if the correspondence survives the rejectors, else -1
+__device__ inline int corr_at(const CorrView& V, const IcpState* __restrict__ st, unsigned e, int* j) {
+  *j = V.nn[e];
+  if (*j < 0) return -1;
+  const unsigned db = __float_as_uint(V.nd[e]);
+  return (db < st->d2star || (db == st->d2star && e < st->istar)) ? (int)e : -1;
+}
+
+__device__ inline void store_partials(const double* v, int nv, double* red, double* __restrict__ part, unsigned blk) {
+  for (int d = 0; d < nv; d++) {
+    const double s = gh_block_sum(v[d], red);
+    if (threadIdx.x == 0) part[(size_t)blk * NPART + d] = s;
+  }
+}
+
+__device__ inline void acc_means_body(const CorrView& V, const IcpState* __restrict__ st, double* __restrict__ part, unsigned blk) {
+  __shared__ double red[16];
+  const unsigned lim = (unsigned)V.ns;
+  double m[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (unsigned e = blk * 256u + threadIdx.x; e < lim; e += NBLK * 256u) {
+    int j;
+    const int i = corr_at(V, st, e, &j);
+    if (i < 0) continue;
+    const float4 S = V.cur[i], D = V.tgt[j];
+    m[0] += (double)S.x; m[1] += (double)S.y; m[2] += (double)S.z;
+    m[3] += (double)D.x; m[4] += (double)D.y; m[5] += (double)D.z;
+    m[6] += (double)V.nd[i];
+  }
+  store_partials(m, 7, red, part, blk);
+}
+
+// sum of component d over the NBLK block partials by one wave: lane l adds blocks l, l+64, ... then a fixed shuffle tree
+__device__ inline double wave_reduce_partials(const double* __restrict__ part, int d) {
+  double s = 0;
+  for (int b = threadIdx.x; b < NBLK; b += 64) s += part[(size_t)b * NPART + d];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+__device__ inline void icp_means_body(IcpState* st, const double* __restrict__ part) {
+  double m[7];
+  for (int d = 0; d < 7; d++) m[d] = wave_reduce_partials(part, d);
+  if (threadIdx.x != 0) return;
+  const double c = (double)st->nv;
+  for (int d = 0; d < 3; d++) { st->msf[d] = (float)(m[d] / c); st->mtf[d] = (float)(m[3 + d] / c); }
+  st->mse = m[6] / c;  // DefaultConvergenceCriteria::calculateMSE over the remaining correspondences
+}
+
+__device__ inline void acc_cov_body(const CorrView& V, const IcpState* __restrict__ st, double* __restrict__ part, unsigned blk) {
+  __shared__ double red[16];
+  const unsigned lim = (unsigned)V.ns;
+  const double ms[3] = {(double)st->msf[0], (double)st->msf[1], (double)st->msf[2]};
+  const double mt[3] = {(double)st->mtf[0], (double)st->mtf[1], (double)st->mtf[2]};
+  double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (unsigned e = blk * 256u + threadIdx.x; e < lim; e += NBLK * 256u) {
+    int j;
+    const int i = corr_at(V, st, e, &j);
+    if (i < 0) continue;
+    const float4 S = V.cur[i], D = V.tgt[j];
+    const double a[3] = {(double)D.x - mt[0], (double)D.y - mt[1], (double)D.z - mt[2]};
+    const double b[3] = {(double)S.x - ms[0], (double)S.y - ms[1], (double)S.z - ms[2]};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int q = 0; q < 3; q++) H[r * 3 + q] += a[r] * b[q];
+  }
+  store_partials(H, 9, red, part, blk);
+}
+
+// TransformationEstimationPointToPlaneLLS: rows [n x s ; n], rhs n.(d - s), float terms summed in f64
+__device__ inline void acc_plane_body(const CorrView& V, const float* __restrict__ tnrm, const IcpState* __restrict__ st, double* __restrict__ part,
+                                      unsigned blk) {
+  __shared__ double red[16];
+  const unsigned lim = (unsigned)V.ns;
+  double acc[28];
+#pragma unroll
+  for (int d = 0; d < 28; d++) acc[d] = 0;
+  for (unsigned e = blk * 256u + threadIdx.x; e < lim; e += NBLK * 256u) {
+    int j;
+    const int i = corr_at(V, st, e, &j);
+    if (i < 0) continue;
+    const float4 S = V.cur[i], D = V.tgt[j];
+    const float nx = tnrm[(size_t)j * 3], ny = tnrm[(size_t)j * 3 + 1], nz = tnrm[(size_t)j * 3 + 2];
+    const double v[6] = {(double)(nz * S.y - ny * S.z), (double)(nx * S.z - nz * S.x), (double)(ny * S.x - nx * S.y), (double)nx, (double)ny, (double)nz};
+    const double dd = (double)(((((nx * D.x + ny * D.y) + nz * D.z) - nx * S.x) - ny * S.y) - nz * S.z);
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+#pragma unroll
+      for (int q = r; q < 6; q++) acc[k++] += v[r] * v[q];
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) acc[21 + r] += v[r] * dd;
+    acc[27] += (double)V.nd[i];
+  }
+  store_partials(acc, 28, red, part, blk);
+}
+
+__device__ inline void mat4_mul(const float* a, const float* b, float* out) {
+  float t[16];
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) t[r * 4 + c] = ((a[r * 4] * b[c] + a[r * 4 + 1] * b[4 + c]) + a[r * 4 + 2] * b[8 + c]) + a[r * 4 + 3] * b[12 + c];
+  for (int d = 0; d < 16; d++) out[d] = t[d];
+}
+
+// closed-form solve + final_transformation_ update + DefaultConvergenceCriteria::hasConverged
+__device__ inline void icp_step_body(IcpState* st, const double* __restrict__ part) {
+  const unsigned cnt = st->nv;
+  double acc[28];
+  const int nacc = st->metric == GHICP_ICP_POINT_TO_POINT ? 9 : 28;
+  for (int d = 0; d < 28; d++) acc[d] = d < nacc ? wave_reduce_partials(part, d) : 0.0;
+  if (threadIdx.x != 0) return;
+  if (cnt < 3u) {  // min_number_correspondences_
+    st->converged = 0; st->reason = GHICP_ICP_NO_CORRESPONDENCES; st->count = 0;
+    return;
+  }
+  float T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  if (st->metric == GHICP_ICP_POINT_TO_POINT) {
+    double A[9], R[9];
+    for (int d = 0; d < 9; d++) A[d] = acc[d] / (double)cnt;
+    gh_quant_grid(A, 9);  // N2: umeyama's sigma is a Matrix3f
+    gh_kabsch(A, R);
+    float Rf[9];
+    for (int d = 0; d < 9; d++) Rf[d] = (float)R[d];
+    for (int r = 0; r < 3; r++) {
+      for (int q = 0; q < 3; q++) T[r * 4 + q] = Rf[r * 3 + q];
+      T[r * 4 + 3] = (float)((double)st->mtf[r] - (((double)Rf[r * 3] * (double)st->msf[0] + (double)Rf[r * 3 + 1] * (double)st->msf[1]) +
+                                                   (double)Rf[r * 3 + 2] * (double)st->msf[2]));
+    }
+  } else {
+    st->mse = acc[27] / (double)cnt;
+    double A[6][6], bb[6], x[6];
+    int k = 0;
+    for (int r = 0; r < 6; r++)
+      for (int q = r; q < 6; q++) { A[r][q] = acc[k]; A[q][r] = acc[k]; k++; }
+    for (int r = 0; r < 6; r++) bb[r] = acc[21 + r];
+    for (int c = 0; c < 6; c++) {  // elimination with partial pivoting (same sequence as the CPU restatement)
+      int piv = c;
+      for (int r = c + 1; r < 6; r++) if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
+      if (piv != c) {
+        for (int q = 0; q < 6; q++) { const double t = A[c][q]; A[c][q] = A[piv][q]; A[piv][q] = t; }
+        const double t = bb[c]; bb[c] = bb[piv]; bb[piv] = t;
+      }
+      for (int r = c + 1; r < 6; r++) {
+        const double f = A[r][c] / A[c][c];
+        for (int q = c; q < 6; q++) A[r][q] -= f * A[c][q];
+        bb[r] -= f * bb[c];
+      }
+    }
+    for (int r = 5; r >= 0; r--) {
+      double s = bb[r];
+      for (int q = r + 1; q < 6; q++) s -= A[r][q] * x[q];
+      x[r] = s / A[r][r];
+    }
+    const double al = x[0], be = x[1], ga = x[2];  // constructTransformationMatrix
+    T[0] = (float)(cos(ga) * cos(be));
+    T[1] = (float)(-sin(ga) * cos(al) + cos(ga) * sin(be) * sin(al));
+    T[2] = (float)(sin(ga) * sin(al) + cos(ga) * sin(be) * cos(al));
+    T[4] = (float)(sin(ga) * cos(be));
+    T[5] = (float)(cos(ga) * cos(al) + sin(ga) * sin(be) * sin(al));
+    T[6] = (float)(-cos(ga) * sin(al) + sin(ga) * sin(be) * cos(al));
+    T[8] = (float)(-sin(be));
+    T[9] = (float)(cos(be) * sin(al));
+    T[10] = (float)(cos(be) * cos(al));
+    T[3] = (float)x[3]; T[7] = (float)x[4]; T[11] = (float)x[5];
+  }
+  for (int d = 0; d < 16; d++) st->T[d] = T[d];
+  mat4_mul(T, st->fin, st->fin);
+  st->iterations++;
+  st->count = 0;
+  const double mse = st->mse, prev = st->prev_mse;
+  if (st->iterations >= st->max_iter) { st->converged = 1; st->reason = GHICP_ICP_ITERATIONS; return; }
+  const double cos_angle = 0.5 * ((double)T[0] + (double)T[5] + (double)T[10] - 1);
+  const double tsq = (double)T[3] * T[3] + (double)T[7] * T[7] + (double)T[11] * T[11];
+  if (cos_angle >= 1.0 - st->eps_t && tsq <= st->eps_t) { st->converged = 1; st->reason = GHICP_ICP_TRANSFORM; return; }
+  if (fabs(mse - prev) < st->eps_e) { st->converged = 1; st->reason = GHICP_ICP_ABS_MSE; return; }
+  if (fabs(mse - prev) / prev < 1e-5) { st->converged = 1; st->reason = GHICP_ICP_REL_MSE; return; }
+  st->prev_mse = mse;
+}
+
+// transformation_ applied to one point: float 4x4 * (x, y, z, 1), the sums in the order of CRegistration::transformcloud
+__device__ inline float4 xf_point(const float* M, float x, float y, float z) {
+  return make_float4(((M[0] * x + M[1] * y) + M[2] * z) + M[3], ((M[4] * x + M[5] * y) + M[6] * z) + M[7], ((M[8] * x + M[9] * y) + M[10] * z) + M[11], 0.f);
+}
+
+__device__ inline void sum_f32_body(const float* __restrict__ v, int n, double* __restrict__ part, unsigned blk) {
+  __shared__ double red[16];
+  double s = 0;
+  for (unsigned e = blk * 256u + threadIdx.x; e < (unsigned)n; e += NBLK * 256u) s += (double)v[e];
+  s = gh_block_sum(s, red);
+  if (threadIdx.x == 0) part[blk] = s;
+}
+
+}  // namespace icpdev
+
+// the fine + coarse grids ghicp_icp searches over a target, built in the context's grid buffers (icp.hip) with the cell chosen from the data
+int gh_icp_build_index(ghicp_ctx* ctx, const float* xyz, long long n, int stride, icpdev::NnIndex* out);

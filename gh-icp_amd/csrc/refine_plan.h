@@ -1,0 +1,32 @@
+// Internal: how ghicp_refine_clouds cuts its pairs into chunks (pairs that share one launch sequence).  Plain C++, no HIP: the planner is
+// compiled on its own by tests/cpp/test_refine_plan.cpp.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+constexpr int kRefineMaxChunk = 4096;                    // one status byte per pair in the context's 4 KB pinned record
+constexpr size_t kRefinePairBytes = 512 * 32 * 8         // the pair's NBLK partial records
+                                    + 6 * 2048 * 4       // its radix-select histograms
+                                    + 1024;              // descriptor, state, counters
+constexpr size_t kRefinePointBytes = 16 + 4 + 4 + 4;     // cur, nn, nd, work list of the coarse search -- per source point
+
+// Chunk boundaries b[0] = 0 < b[1] < ... < b.back() = n_pairs over the pairs in the given order (empty list: {0}).  max_concurrent > 0: chunks of
+// exactly that many pairs (the last one shorter), capped at kRefineMaxChunk.  0: as many pairs per chunk as fit `budget` bytes by the per-pair
+// and per-point costs above, at least one.  ns[p]: source points of pair p.
+inline std::vector<int> gh_refine_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget) {
+  std::vector<int> b(1, 0);
+  if (n_pairs <= 0) return b;
+  const int cap = max_concurrent > 0 && max_concurrent < kRefineMaxChunk ? max_concurrent : kRefineMaxChunk;
+  size_t used = 0;
+  int in_chunk = 0;
+  for (int p = 0; p < n_pairs; p++) {
+    const size_t cost = kRefinePairBytes + kRefinePointBytes * (size_t)(ns[p] > 0 ? ns[p] : 0);
+    const bool full = in_chunk >= cap || (max_concurrent <= 0 && in_chunk > 0 && used + cost > budget);
+    if (full) { b.push_back(p); used = 0; in_chunk = 0; }
+    used += cost;
+    in_chunk++;
+  }
+  b.push_back(n_pairs);
+  return b;
+}

@@ -446,6 +446,34 @@ int ghicp_register_clouds(ghicp_ctx* ctx, const ghicp_pair_config* cfg, int32_t 
                           const ghicp_cloud* const* T, ghicp_pair_stats* stats);
 
 /* ------------------------------------------------------------------------------------------------
+ * Coarse-to-fine over cached clouds: the loop of ghicp_icp for many pairs of handles at once, from the poses ghicp_register_clouds
+ * returned.  Same results as, per pair, ghicp_cloud_download + ghicp_transform_cloud_f32(source, float(Rt_init)) + ghicp_icp against the
+ * target's down-sampled cloud, bit for bit.  (The reference runs icp_reg / ptplicp_reg pair by pair; it has no counterpart.)
+ * ------------------------------------------------------------------------------------------------ */
+/* Builds what `cloud` needs to serve as a TARGET and keeps it in the handle: the 1-NN search grids over its down-sampled points and, for
+ * covariance_k in 1..20, the k-NN normals ghicp_icp computes for ptplicp_reg (0: none).  Calling it again with another k replaces the
+ * normals and keeps the grids.  ghicp_cloud_recompute / ghicp_clouds_recompute invalidate the prepared state, ghicp_cloud_destroy frees
+ * it.  The handle is synchronised on return.  GHICP_ERR_ARG for a handle rebuilt by ghicp_cloud_from_features (it holds no points). */
+int ghicp_cloud_prepare_refine(ghicp_cloud* cloud, int32_t covariance_k);
+
+typedef struct ghicp_refine_result {
+  float T_icp[16];        /* ICP's final_transformation_ (row-major), on top of float(Rt_init); identity for a refused pair */
+  double Rt_refined[16];  /* double(T_icp) * double(float(Rt_init)), f64 on the host: the refined source->target pose */
+  ghicp_icp_stats stats;  /* as ghicp_icp fills it; done = 0: refused by the overlap gate */
+} ghicp_refine_result;
+
+/* S[p] -> T[p] for n_pairs pairs, from Rt_init (n_pairs x 16 row-major f64 [host], the Rt of ghicp_pair_stats; NULL: identity for every
+ * pair).  Both metrics, use_trimmed 0 / 1 (with the overlap gate: a refused pair gets done = 0, T_icp = I, Rt_refined = the float-rounded
+ * init).  NOT covered: use_reciprocal != 0 -- the reciprocal test needs a grid over the moved source per pair per iteration, a launch
+ * sequence per pair; it gets GHICP_ERR_ARG (use ghicp_icp).  GHICP_ERR_ARG also for a target that is not prepared, for point-to-plane
+ * with normals prepared for a k other than params->covariance_k, and for handles of another device; nothing is written then.  The
+ * handles are const: nothing is built lazily, so prepared handles may be shared between contexts of the device.
+ * max_concurrent: pairs that share one launch sequence (chunks of that size, in the given order; at most 4096); 0: chosen from the free
+ * device memory.  Results do not depend on it.  out: n_pairs [host]. */
+int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                        const double* Rt_init /*[host]*/, int32_t max_concurrent, ghicp_refine_result* out /*[host]*/);
+
+/* ------------------------------------------------------------------------------------------------
  * Pair queue: independent scan pairs sharded over the GPUs of ONE node, one process per GPU (BASELINE configs[3]).
  * The reference registers one pair per process run (test/ghicp_main.cpp:56-160) and has no counterpart; a caller of the drop-in
  * headers that holds MANY pairs shards them with these calls.  Pairs share nothing, so there is NO collective on the data path --
