@@ -92,7 +92,7 @@ enum BufSlot {
 
 enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_FD_BSC, KT_NMS_ROUND, KT_VOXEL_SORT,
               KT_FB_VOXEL, KT_FB_GRID, KT_FB_PRUNE, KT_FB_RANK, KT_FB_OUT,  // stages of the batched front end (batch.hip) around the kernels above
-              KT_PAIR_LOOP,                                                  // the persistent pair loop (loop.hip): all classes of a batch, fork -> join
+              KT_PAIR_LOOP,                                                  // the persistent pair loop (pair_loop.hip): all classes of a batch, fork -> join
               KT_TRANSFORM,                                                  // S7 of a batch (ghicp_transform_clouds)
               KT_PAIR_LOOP_DISPATCH,                                         // ONE k_pair_loop dispatch (a class launch of a batch), timed on the stream it runs on -- what rocprofv3's kernel trace reports per row
               KT_REFINE,                                                     // one chunk of the batched fine registration (refine.hip): upload -> final states
@@ -178,7 +178,7 @@ struct ghicp_ctx {
   hipStream_t confine_stream = nullptr, rest_stream = nullptr;  // masks: the confined class's CUs / all the others (the pair in use, owned by confine_cache)
   int confine_cus = 0;
   struct ConfinePair { int cus; hipStream_t confined, rest; };
-  std::vector<ConfinePair> confine_cache;  // one masked stream pair per share B seen (loop.hip run_pair_loop)
+  std::vector<ConfinePair> confine_cache;  // one masked stream pair per share B seen (pair_loop.hip run_pair_loop)
   // Compact LDS layout of the Kuhn-Munkres state (km4_dev.h: 36 instead of 44 B per row, sty and tlo in a per-slot global region, buffer
   // B_KM_SLACK): graphs of n = 925..1131 then fit four to a CU and join the one four-per-CU class.  GHICP_KM_COMPACT=0 switches it off (the
   // planning of round 6: A/B measurements); GHICP_KM_COMPACT_FROM=<n> is the test hook that FORCES the compact layout on every graph of n rows
@@ -381,7 +381,7 @@ struct gh_loop_job {
   int32_t* converged;
   int32_t* matchlist;
   double* rmse_after;  // host, optional: RMSEafter of the last iteration (ghicp_reg.cpp:905, the value behind "Registration Succeed.")
-  // resumed loops (ghicp_iterate): scalar loop state in / out (host, opaque LoopState of loop.hip), the moved source keypoints out (device),
+  // resumed loops (ghicp_iterate): scalar loop state in / out (host, opaque LoopState of loop_dev.h), the moved source keypoints out (device),
   // the last iteration's record (host), and the iteration whose matches go to matchlist row 0
   const void* resume_in;
   void* resume_out;

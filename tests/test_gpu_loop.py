@@ -265,7 +265,7 @@ def test_km_beyond_the_lds_resident_solver(ctx, oracle):
 
 
 def test_pair_loop_persistent_batch(ctx, api, synth, oracle):
-    """The persistent pair loop (loop.hip:k_pair_loop; Kuhn-Munkres batches): pairs of very different sizes in ONE batch -- several
+    """The persistent pair loop (pair_loop.hip:k_pair_loop; Kuhn-Munkres batches): pairs of very different sizes in ONE batch -- several
     LDS-occupancy classes, each its own launch and queue, more pairs than one class has slots for is not needed for the logic -- against
     the oracle pair by pair (iterations, every iteration's transform, final 4x4), and the batch against the same pairs registered alone."""
     rng = np.random.default_rng(21)
@@ -385,7 +385,7 @@ def test_one_slot_takes_many_pairs_in_any_order(api, synth, oracle, order):
 
 
 def test_confined_three_per_cu_class_changes_nothing_but_the_schedule(api, synth, oracle):
-    """Round 5: graphs that fit only three slots per CU run on their own CUs (masked streams, loop.hip:run_pair_loop) and the four-per-CU
+    """Round 5: graphs that fit only three slots per CU run on their own CUs (masked streams, pair_loop.hip:run_pair_loop) and the four-per-CU
     class on the others -- where a slot runs cannot reach a result: the same batch through a context with GHICP_LOOP_CONFINE=0 (one launch per
     class on every CU, as in round 4) and through a default context gives the same iterations and the same 4x4 bits, pair by pair."""
     import os

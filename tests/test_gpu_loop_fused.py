@@ -1,4 +1,4 @@
-"""The persistent pair loop's fused stages (loop.hip: pl_sweep_km / pl_graph_km -- one combined-distance pass per iteration decides the graph's
+"""The persistent pair loop's fused stages (pair_loop.hip: pl_sweep_km / pl_graph_km -- one combined-distance pass per iteration decides the graph's
 membership while it takes the sums, the fill reads the row bitmask) against the three passes of before (GHICP_LOOP_FUSE=0: pl_sweep / pl_graph):
 every field of every iteration record, the iteration count, the 4x4 and the match lists must be the SAME BITS.  The shapes stand at the edges
 of the code's tiles: the 256-row blocks, the 512-column chunk, the padding rows of ks < kt and ks > kt, the 32-bit mask word and the 64-column

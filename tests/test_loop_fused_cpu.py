@@ -1,5 +1,5 @@
-"""CPU-suite companion of tests/test_gpu_loop_fused.py: the same cases on the host SIMT interpreter (the library's own loop.hip compiled for the
-host), in two lane orders -- the fused stages of the persistent pair loop against its three passes of before, bit for bit."""
+"""CPU-suite companion of tests/test_gpu_loop_fused.py: the same cases on the host SIMT interpreter (the library's own pair_loop.hip and loop.hip compiled
+for the host), in two lane orders -- the fused stages of the persistent pair loop against its three passes of before, bit for bit."""
 import os
 import subprocess
 import sys
