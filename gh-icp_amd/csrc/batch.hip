@@ -286,8 +286,8 @@ __global__ __launch_bounds__(256) void k_fb_prune_flags(const float* __restrict_
   flags[i] = (r1 < ratio_max && r2 < ratio_max && count[i] > min_n) ? 1 : 0;
 }
 
-__device__ inline unsigned long long fb_f64_key(double v) {  // order-preserving f64 -> u64 (nms.hip)
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+__device__ inline unsigned long long fb_f64_key(double v) {  // order-preserving f64 -> u64, -0.0 keyed as +0.0 (nms.hip)
+  const unsigned long long b = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 

@@ -6,7 +6,9 @@
 // emit the best unsuppressed one and erase everything within R of it.  Greedy NMS over a strict total
 // order is the unique fixed point of
 //     selected(i)  <=>  no selected j with rank(j) < rank(i) and d2(i,j) < R^2          
-// and is computed by ONE workgroup per cloud that sweeps the rank-ordered candidates in chunks (nms_dev.h).
+// and is computed in two ways: here by ONE workgroup per cloud that sweeps the rank-ordered candidates in chunks (nms_dev.h: ghicp_nms,
+// ghicp_keypoints, the pair API, ghicp_cloud_recompute), and in batch.hip by decision rounds with one thread per candidate over every cloud
+// of a batch at once (k_fb_nmsr_*: ghicp_clouds_recompute).  Same keypoints in the same order either way (tests/test_gpu_nms.py).
 // Rank = (curvature desc, candidate order asc): stable radix sort, so ties resolve to the lower point index.
 #include "grid.h"
 
@@ -21,9 +23,10 @@
 
 namespace {
 
-// order-preserving map f64 -> u64 (ascending); NaN never reaches here (prune rejects it)
+// order-preserving map f64 -> u64 (ascending); NaN never reaches here (prune rejects it).  -0.0 takes the key of +0.0: the reference's
+// comparator (>) holds them equal, so candidate order decides between them as inside any other plateau
 __device__ inline unsigned long long f64_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned long long b = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 

@@ -78,6 +78,20 @@ def test_solver_fuzz_in_reverse_lane_order():
     assert r.returncode == 0 and "2 passed" in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 
+def test_batched_nms_rounds_in_reverse_lane_order():
+    """The batched NMS tests (Part B of tests/test_gpu_nms.py) with the interpreter running waves and lanes in REVERSE order: the decision
+    rounds of batch.hip claim that any order of decisions gives the same keypoints -- chains, plateaus, rank tiles, offsets inside a batch."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from hipsim import build
+
+    build.build()
+    env = dict(os.environ, GHICP_SIM="1", HIPSIM_ORDER="reverse", HIPSIM_THREADS="2")
+    cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_nms.py"), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
+           "-k", "test_batch_"]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "6 passed" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
 def test_bench_py_on_the_host_simt_interpreter():
     """bench.py itself (calibration of the two front ends, pipeline threads, batched front end, record gather, the JSON line) against the
     simulated library: its host logic is exercised before it ever meets the GPU box.  The numbers mean nothing."""
