@@ -3,87 +3,31 @@
 //
 // Why: one cloud's front end is ~100 device operations (24 kernels, 3 radix sorts, 4 selects, copies, 7 host synchronisations that size
 // the next stage) and the host issues them at ~8 us each, so a cloud costs 0.85 ms however many streams submit clouds.
-// Here the clouds of a batch are CONCATENATED: every elementwise kernel, sort and select runs once over all their points, the kernels
-// that work per cell / per cloud / per keypoint (gh_pca_cell, gh_nms_greedy_cloud, gh_bsc_keypoint -- the same device code as the
-// single-cloud path) look their cloud up in a descriptor block, and the six host synchronisations serve the whole batch.
+// Here the clouds of a batch are CONCATENATED: every elementwise kernel, sort and select runs once over all their points, and the kernels
+// that work per cell / per keypoint (gh_pca_cell_body, gh_bsc_keypoint -- the same device code as the single-cloud path) look their cloud
+// up in a descriptor block.
 //   * voxel keys carry the cloud id above the voxel key's bits  -> one stable radix sort keeps clouds apart and ordered;
 //   * grid cells are numbered globally (cell base of the cloud + cell) -> one sort / one cell table per grid for all clouds;
-//   * NMS ranks: one 64-bit descending sort of all candidates by curvature, then one stable pass over the cloud id.
+//   * NMS: decision rounds with one thread per candidate over every cloud of the batch, not the one-workgroup sweep of the single-cloud
+//     path (batch_nms.hip has the design).
 // FPFH clouds: the kNN grid is the batch's second grid and the normal / SPFH / FPFH kernels of fpfh.hip run once over the concatenated cloud.
+// Host synchronisations of a batch: three reports that size the next stage (raw boxes; down-sampled counts and boxes; candidate counts),
+// one per launch sequence of FB_NMS_ROUNDS NMS rounds (one sequence settles a scan), and the last one before the handles are handed back.
 // Results are bit-identical to ghicp_cloud_recompute() cloud by cloud: same per-cloud boxes, same grids, same orders inside a cell,
 // same reduction trees (tests/test_gpu_batch.py).
-#include "cloud.h"
-#include "grid.h"
-#include "devmath.h"
+// Where things live: batch_dev.h has the descriptor block, the report and the state of a batch in flight (FbRun); batch_nms.hip the NMS
+// rounds; this file the other kernels, one host function per stage (fb_*, in the order they run) and the C entry point.
+#include "batch_dev.h"
+#include "frontend.h"
 #include "pca_dev.h"
-#include "nms_dev.h"
 #include "bsc_dev.h"
 #include "prims.h"
 
-
 #include <cmath>
-#include <vector>
-
-
-float gh_fpfh_cell(const float* mm, long long m);  // fpfh.hip
-int gh_fpfh_batch_dev(ghicp_ctx* ctx, const float4* dsg, int M, const float4* pts, const unsigned* start, const GridDesc* gd_dev, const unsigned* cell_base_dev,
-                      const int* moff_dev, int nb, float* hist);
 
 namespace {
 
-constexpr int FB_MAX = 64;  // clouds per batch
-constexpr int FB_NMS_ROUNDS = 16;  // NMS rounds per launch sequence (the host looks at the last one's count and launches another sequence if need be)
-
-struct FbCloud {
-  const float* xyz;  // raw cloud
-  int n, stride;
-  float vmn[3], vinv;              // voxel filter (filter.hpp:28-40)
-  unsigned long long mul_x, mul_y;
-  float4* ds;                      // outputs: the cloud handle's buffers
-  int* kp;
-  double* kpx;
-  uint8_t* feat;
-};
-
-// Host -> device descriptor block (uploaded once per stage) ...
-struct FbBlock {
-  FbCloud c[FB_MAX];
-  GridDesc g1[FB_MAX], g2[FB_MAX], g3[FB_MAX];  // PCA grid, BSC grid, NMS grid of selected keypoints
-  int roff[FB_MAX + 1];                         // raw points
-  int hoff[FB_MAX + 1];                         // voxel run heads (device written)
-  int moff[FB_MAX + 1];                         // down-sampled points (device written)
-  int coff[FB_MAX + 1];                         // NMS candidates (device written)
-  int koff[FB_MAX + 1];                         // keypoints
-  unsigned cb1[FB_MAX + 1], cb2[FB_MAX + 1], hb[FB_MAX + 1];  // cell bases of the three grids
-  int nb, pad_;
-};
-// ... and what the device reports back
-struct FbOut {
-  int bb[FB_MAX * 6];
-  int hoff[FB_MAX + 1], moff[FB_MAX + 1], coff[FB_MAX + 1];
-  int kcount[FB_MAX];
-  int nms_und[FB_NMS_ROUNDS];  // candidates each NMS round of the last sequence left undecided
-};
-
-// largest b in [0, nb) with off[b] <= i (off ascending; clouds without items are skipped over)
-__device__ inline int fb_find(const int* __restrict__ off, int nb, int i) {
-  int lo = 0, hi = nb - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-__device__ inline int fb_find_u(const unsigned* __restrict__ off, int nb, unsigned i) {
-  int lo = 0, hi = nb - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
+enum { FB_CLOUD_BY_CLOUD = -1, FB_HALVE = -2 };  // a stage's verdict that the batch as it stands is not covered: the entry point takes the fall-back
 
 __global__ void k_fb_bbox_init(int* __restrict__ bb, int nb) {  // enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3 per cloud
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -286,253 +230,6 @@ __global__ __launch_bounds__(256) void k_fb_prune_flags(const float* __restrict_
   flags[i] = (r1 < ratio_max && r2 < ratio_max && count[i] > min_n) ? 1 : 0;
 }
 
-__device__ inline unsigned long long fb_f64_key(double v) {  // order-preserving f64 -> u64, -0.0 keyed as +0.0 (nms.hip)
-  const unsigned long long b = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// ------------------------------------------------------------------------------------------------ NMS over the whole chip (round 6)
-// Greedy non-maximum suppression (keypoint_detect.hpp:149-191) = the lexicographically first maximal independent set of the graph
-// "candidates closer than R", taken in rank order (curvature descending, ties: lower point index).  It is the unique fixed point of
-//     selected(i)   <=>  every neighbour of higher rank is suppressed
-//     suppressed(i) <=>  some neighbour of higher rank is selected                                              
-// and both facts are FINAL once established, so they may be established in any order by any number of threads: a candidate decides as
-// soon as its higher-ranked neighbours have.  One thread per candidate, every cloud of the batch in the same launches, a handful of
-// rounds (the longest chain of decisions a scan needs: 6-11 with synchronous rounds, fewer here because a round sees the decisions
-// of the waves that ran before it).  Rounds 2-5 walked the rank-ordered candidates of a cloud with ONE workgroup (nms_dev.h, still the
-// single-cloud path): 1.6-2.5 ms per launch with 224 CUs idle -- round-5 verdict, weak #6 / item 7.
-//   * candidates are bucketed by cell (side R * 1.0001, the cloud's own grid over the box of its down-sampled points) by a counting
-//     sort: histogram, hand-written scan (prims.hip), scatter -- the order inside a cell does not matter, every test is order free;
-//   * "suppressed" is decided against per-cell lists of the SELECTED candidates (1-3 entries around a point); "selected" by ONE walk over
-//     the neighbouring cells, spread over the rounds: the walk stops at a neighbour of higher rank that is not suppressed and goes on
-//     behind it once that neighbour has been suppressed (k_fb_nmsr_round);
-//   * the keypoints of a cloud leave in rank order: each selected candidate counts the selected ones of its cloud that outrank it.
-// Same set AND order as the greedy sweep (tests/test_gpu_batch.py, test_golden.py: keypoint ids == oracle).
-struct NmsrArgs {
-  const float4* dsg;          // concatenated down-sampled clouds
-  const int* cand;            // candidate -> global point index, ascending
-  const double* curv;
-  int ctot;
-  unsigned* table;            // [0] = 0, [1 + cell]: histogram -> end -> start of the cell's run (see k_fb_nmsr_fill)
-  unsigned* ccell;            // candidate -> global cell
-  unsigned long long* ckey;   // candidate -> rank key (order-preserving image of the curvature)
-  float4* spts;               // slot -> (x, y, z, candidate id); inside a cell the slots are in RANK order (k_fb_nmsr_sort)
-  unsigned long long* skey;   // slot -> rank key
-  float4* spts0;              // the same two arrays as the scatter left them (cell by cell, arbitrary order inside a cell)
-  unsigned long long* skey0;
-  unsigned char* state;       // slot -> 0 undecided, 1 selected, 2 suppressed
-  int* head;                  // cell -> most recently selected slot, -1: none
-  int* next;                  // slot -> next selected slot of its cell
-  int* blk;                   // slot -> the neighbour of higher rank this candidate is waiting for (-1: has not looked yet)
-  unsigned* upos;             // slot -> where its scan of the neighbouring cells goes on (slot index) ...
-  unsigned char* urun;        // ... and in which of the nine runs
-  int* sel;                   // per cloud (at coff[b]): the selected slots, in no particular order
-  int* kcount;                // per cloud: selected so far
-  int* undecided;             // per round: candidates the round left undecided
-};
-
-__global__ __launch_bounds__(256) void k_fb_nmsr_keys(const FbBlock* __restrict__ D, NmsrArgs A) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= A.ctot) return;
-  const int b = fb_find(D->coff, D->nb, i);
-  const GridDesc& g = D->g3[b];
-  const int pid = A.cand[i];
-  const float4 P = A.dsg[pid];
-  const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
-  const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
-  const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
-  const unsigned cell = D->hb[b] + (((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz);
-  A.ccell[i] = cell;
-  A.ckey[i] = fb_f64_key(A.curv[pid]);
-  atomicAdd(&A.table[1 + cell], 1u);
-}
-
-// after the inclusive scan table[1 + c] is the END of cell c's run; every candidate takes the slot below the current end, which leaves
-// table[1 + c] = START of cell c = end of cell c - 1: T = table + 1 is then the usual cell table (T[c] .. T[c + 1]), T[ncell] = ctot
-__global__ __launch_bounds__(256) void k_fb_nmsr_fill(NmsrArgs A, unsigned ncell) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) A.table[1 + ncell] = (unsigned)A.ctot;
-  if (i >= A.ctot) return;
-  const unsigned t = atomicSub(&A.table[1 + A.ccell[i]], 1u) - 1u;
-  const float4 P = A.dsg[A.cand[i]];
-  A.spts0[t] = make_float4(P.x, P.y, P.z, __int_as_float(i));
-  A.skey0[t] = A.ckey[i];
-}
-
-// Inside a cell the candidates go in RANK order (highest first): every candidate counts the members of its cell that outrank it -- cells
-// hold ~10 candidates, a few hundred at most -- and takes that position.  A walk over a cell can then stop at the first entry of lower
-// rank, so a candidate near the top of its neighbourhood (the ones that stay undecided longest, and the ones that end up selected)
-// looks at a handful of entries per cell instead of all of them (call 6 of round 6: rounds 2-9 were 100-220 us each, held up by the
-// few candidates per wave that had to walk their whole neighbourhood, ~200 entries, to find nobody left above them).
-__global__ __launch_bounds__(256) void k_fb_nmsr_sort(NmsrArgs A) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= A.ctot) return;
-  const float4 P = A.spts0[t];
-  const int id = __float_as_int(P.w);
-  const unsigned long long key = A.skey0[t];
-  const unsigned c = A.ccell[id];
-  const unsigned ub = A.table[1 + c], ue = A.table[2 + c];
-  unsigned rank = 0;
-  for (unsigned u = ub; u < ue; u++) {
-    const unsigned long long ku = A.skey0[u];
-    rank += (ku > key || (ku == key && __float_as_int(A.spts0[u].w) < id)) ? 1u : 0u;
-  }
-  const unsigned d = ub + rank;
-  A.spts[d] = P;
-  A.skey[d] = key;
-  A.state[d] = 0;
-  A.blk[d] = -1;
-  A.next[d] = -1;
-  A.urun[d] = 0;
-  A.upos[d] = 0u;
-}
-
-// One round, for every candidate that has not decided yet:
-//   (1) a SELECTED neighbour (per-cell lists of the selected candidates, 1-3 entries around a point) -> suppressed.  A selected neighbour
-//       of an undecided candidate always outranks it (nothing is selected next to an undecided candidate of higher rank);
-//   (2) otherwise the candidate walks the entries of its nine runs ONCE over all rounds: it stops at the first neighbour of higher rank
-//       that is not suppressed and WAITS for it (blk; the position is kept in urun / upos).  The next round looks at that neighbour's
-//       state first (one load) and walks on behind it only if it has been suppressed: whatever lies before that position was out of
-//       range, of lower rank or suppressed -- all final;
-//   (3) the walk reaches the end: every neighbour of higher rank is suppressed -> selected.
-// Measured on 32 cfg2 clouds (0.96 M candidates): a full re-scan in every round (call 3) visits 380 M entries, 2.9 ms; the walk without
-// step (1) (call 4) needs a round per link of a chain of waiting candidates, hundreds of rounds; with both, a suppression shows one
-// round after the selection that causes it and an entry is visited at most once per candidate.
-__global__ __launch_bounds__(256) void k_fb_nmsr_round(const FbBlock* __restrict__ D, NmsrArgs A, float r2, int round, int first) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  int waiting = 0;  // no early return: the wave counts its waiting lanes with ONE atomic at the end
-  if (t < A.ctot && A.state[t] == 0) {
-    const float4 P = A.spts[t];
-    const int id = __float_as_int(P.w);
-    const int b = fb_find(D->coff, D->nb, id);
-    const GridDesc g = D->g3[b];
-    const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
-    const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
-    const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
-    int* H = A.head + D->hb[b];
-    int verdict = 0;  // 0 go on, 1 wait, 2 suppressed
-    if (!first) {     // (1); plain loads: a stale list only postpones the decision by a round.  All 27 list heads are asked for at once
-      int hd[27];     // (independent loads: one round trip to L2 instead of 27 dependent ones -- the round is bound by load latency)
-#pragma unroll
-      for (int r = 0; r < 9; r++) {
-        const int x = cx - 1 + r / 3, y = cy - 1 + r % 3;
-        const bool in = x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1];
-        const unsigned base = in ? ((unsigned)x * g.dim[1] + y) * g.dim[2] : 0u;
-#pragma unroll
-        for (int dz = 0; dz < 3; dz++) {
-          const int z = cz - 1 + dz;
-          hd[r * 3 + dz] = (in && z >= 0 && z < g.dim[2]) ? H[base + z] : -1;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 27; q++)
-        for (int j = hd[q]; j >= 0 && verdict == 0; j = A.next[j]) {
-          const float4 Q = A.spts[j];
-          const float dx = Q.x - P.x, dy = Q.y - P.y, dz = Q.z - P.z;
-          float d2 = dx * dx;
-          d2 += dy * dy;
-          d2 += dz * dz;
-          if (d2 < r2) verdict = 2;
-        }
-    }
-    if (verdict == 0) {  // (2)
-      const int bl = A.blk[t];
-      if (bl >= 0) {
-        const int sb = A.state[bl];
-        verdict = sb == 0 ? 1 : (sb == 1 ? 2 : 0);
-      }
-    }
-    if (verdict == 0) {
-      const unsigned long long key = A.skey[t];
-      const unsigned* T = A.table + 1 + D->hb[b];
-      unsigned tb[9][4];  // the cell table around the candidate: nine columns x (three cells + 1), asked for at once
-#pragma unroll
-      for (int q = 0; q < 9; q++) {
-        const int x = cx - 1 + q / 3, y = cy - 1 + q % 3;
-        const bool in = x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1];
-        const unsigned base = in ? ((unsigned)x * g.dim[1] + y) * g.dim[2] : 0u;
-#pragma unroll
-        for (int dz = 0; dz < 4; dz++) {
-          const int z = cz - 1 + dz;
-          tb[q][dz] = (in && z >= 0 && z <= g.dim[2]) ? T[base + z] : 0u;
-        }
-      }
-      const int c_from = A.urun[t];  // cell 0..26 the walk stands in
-      const unsigned u_res = A.upos[t];
-#pragma unroll
-      for (int c = 0; c < 27; c++) {
-        if (verdict != 0 || c < c_from) continue;
-        const int q = c / 3, dz = c % 3;
-        const int z = cz - 1 + dz;
-        if (z < 0 || z >= g.dim[2]) continue;
-        const unsigned ub = tb[q][dz], ue = tb[q][dz + 1];
-        // four entries per step, everything a verdict may need asked for at once (position, rank key, state: independent loads); they
-        // are LOOKED AT in slot order = rank order, and the cell is left at the first entry that does not outrank this candidate
-        bool below = false;
-        for (unsigned u0 = max(ub, c == c_from ? u_res : 0u); u0 < ue && verdict == 0 && !below; u0 += 4u) {
-          float4 Q[4];
-          unsigned long long K[4];
-          int S[4];
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            const unsigned u = min(u0 + (unsigned)e, ue - 1u);
-            Q[e] = A.spts[u]; K[e] = A.skey[u]; S[e] = A.state[u];
-          }
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            const unsigned u = u0 + (unsigned)e;
-            if (verdict != 0 || below || u >= ue) continue;
-            if (!(K[e] > key || (K[e] == key && __float_as_int(Q[e].w) < id))) { below = true; continue; }  // this entry and the rest of the cell rank lower (or it is the candidate itself)
-            const float dx = Q[e].x - P.x, dy = Q[e].y - P.y, dz2 = Q[e].z - P.z;
-            float d2 = dx * dx;
-            d2 += dy * dy;
-            d2 += dz2 * dz2;
-            if (!(d2 < r2)) continue;
-            if (S[e] == 2) continue;
-            if (S[e] == 1) { verdict = 2; continue; }
-            A.blk[t] = (int)u; A.urun[t] = (unsigned char)c; A.upos[t] = u + 1u;
-            verdict = 1;
-          }
-        }
-      }
-      if (verdict == 0) {  // (3)
-        A.state[t] = 1;
-        const int old = atomicExch(&H[((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz], t);
-        A.next[t] = old;
-        A.sel[D->coff[b] + atomicAdd(&A.kcount[b], 1)] = t;
-      }
-    }
-    if (verdict == 2) A.state[t] = 2;
-    waiting = verdict == 1;
-  }
-  const unsigned long long wm = __ballot(waiting != 0);
-  if ((threadIdx.x & 63) == 0 && wm) atomicAdd(&A.undecided[round], (int)__popcll(wm));
-}
-
-// keypoints of cloud b in rank order: position = number of selected candidates of the cloud that outrank this one
-__global__ __launch_bounds__(256) void k_fb_nmsr_rank(const FbBlock* __restrict__ D, NmsrArgs A, int* __restrict__ kpg) {
-  __shared__ unsigned long long s_key[1024];
-  __shared__ int s_id[1024];
-  const int b = blockIdx.x;
-  const int K = A.kcount[b], c0 = D->coff[b];
-  for (int base = blockIdx.y * 256; base < K; base += 256 * gridDim.y) {  // (the trip count is uniform over the workgroup: barriers below)
-    const int k = base + threadIdx.x;
-    unsigned long long key = 0;
-    int id = 0;
-    if (k < K) { const int t = A.sel[c0 + k]; key = A.skey[t]; id = __float_as_int(A.spts[t].w); }
-    int rank = 0;
-    for (int q0 = 0; q0 < K; q0 += 1024) {
-      __syncthreads();
-      for (int q = threadIdx.x; q < min(1024, K - q0); q += 256) { const int t = A.sel[c0 + q0 + q]; s_key[q] = A.skey[t]; s_id[q] = __float_as_int(A.spts[t].w); }
-      __syncthreads();
-      const int m = min(1024, K - q0);
-      if (k < K)
-        for (int q = 0; q < m; q++) rank += (int)(s_key[q] > key) | ((int)(s_key[q] == key) & (int)(s_id[q] < id));
-    }
-    if (k < K) kpg[c0 + rank] = A.cand[id] - D->moff[b];
-  }
-}
-
 __global__ __launch_bounds__(256) void k_fb_copy_ds(const FbBlock* __restrict__ D, const float4* __restrict__ dsg, int M) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= M) return;
@@ -580,12 +277,6 @@ __global__ __launch_bounds__(BT) void k_fb_bsc(const FbBlock* __restrict__ D, co
   gh_bsc_keypoint(G, C, q - D->koff[b], D->koff[b + 1] - D->koff[b], D->c[b].feat, lcs + (size_t)D->koff[b] * 12);
 }
 
-int bits_for(unsigned long long maxv) {
-  int b = 1;
-  while (b < 64 && (maxv >> b) != 0ull) b++;
-  return b;
-}
-
 void decode_box(const int* enc, float* mm) {
   for (int k = 0; k < 6; k++) {
     const int i = enc[k] >= 0 ? enc[k] : enc[k] ^ 0x7fffffff;
@@ -616,47 +307,33 @@ int build_grid(ghicp_ctx* ctx, const FbBlock* D, int which, const float4* dsg, i
   return GHICP_OK;
 }
 
+int fb_cloud_by_cloud(int n_clouds, ghicp_cloud* const* clouds, const float* const* xyz, const int64_t* n, int stride) {
+  for (int i = 0; i < n_clouds; i++) GH_TRY(ghicp_cloud_recompute(clouds[i], xyz[i], n[i], stride));
+  return GHICP_OK;
+}
+
+// two batches of half the clouds (a single cloud always fits: n < 2^31 - 2, and gh_grid_desc limits it to 2^26 cells per grid)
+int fb_halve(ghicp_ctx* ctx, int n_clouds, ghicp_cloud* const* clouds, const float* const* xyz, const int64_t* n, int stride) {
+  if (n_clouds == 1) return ghicp_cloud_recompute(clouds[0], xyz[0], n[0], stride);
+  const int half = n_clouds / 2;
+  GH_TRY(ghicp_clouds_recompute(ctx, half, clouds, xyz, n, stride));
+  return ghicp_clouds_recompute(ctx, n_clouds - half, clouds + half, xyz + half, n + half, stride);
+}
+
 }  // namespace
 
-// Front ends of n_clouds raw clouds (device pointers xyz[i], n[i] points of `stride` floats) into existing handles of ONE front-end
-// configuration and one context.  Equivalent to ghicp_cloud_recompute(clouds[i], xyz[i], n[i], stride) for every i, bit for bit.
-extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cloud* const* clouds, const float* const* xyz, const int64_t* n, int stride) {
-  GH_ENTER(ctx);
-  GH_ARG(n_clouds >= 0 && (n_clouds == 0 || (clouds != nullptr && xyz != nullptr && n != nullptr)) && stride >= 3);
-  if (n_clouds == 0) return GHICP_OK;
-  long long N = 0;
-  for (int i = 0; i < n_clouds; i++) {
-    GH_ARG(clouds[i] != nullptr && clouds[i]->ctx == ctx && n[i] >= 0 && n[i] < (1ll << 31) - 2);
-    if (!same_front_end(clouds[i]->cfg, clouds[0]->cfg))
-      return ctx->fail(GHICP_ERR_ARG, "ghicp_clouds_recompute: cloud %d has a different front-end configuration", i);
-    for (int j = 0; j < i; j++) GH_ARG(clouds[j] != clouds[i]);
-    N += n[i];
-  }
-  const ghicp_pair_config cfg = clouds[0]->cfg;
-  // what the batch does not cover goes cloud by cloud: no down-sampling, host pointers
-  if (!(cfg.voxel > 0.f) || ctx->host_ptrs) {
-    for (int i = 0; i < n_clouds; i++) GH_TRY(ghicp_cloud_recompute(clouds[i], xyz[i], n[i], stride));
-    return GHICP_OK;
-  }
-  if (n_clouds > FB_MAX || N + n_clouds >= (1ll << 31) - 2) {  // split (a single cloud always fits: n < 2^31 - 2)
-    if (n_clouds == 1) return ghicp_cloud_recompute(clouds[0], xyz[0], n[0], stride);
-    const int half = n_clouds / 2;
-    GH_TRY(ghicp_clouds_recompute(ctx, half, clouds, xyz, n, stride));
-    return ghicp_clouds_recompute(ctx, n_clouds - half, clouds + half, xyz + half, n + half, stride);
-  }
-  const int nb = n_clouds;
-  hipStream_t s = ctx->stream;
-  // pinned mirror of the descriptor block and of the report
+// pinned mirror of the descriptor block and of the report, their device block; the handles reset, the raw clouds described
+int FbRun::begin(const float* const* xyz, const int64_t* n, int stride) {
   if (!ctx->fb_pinned) {
     if (hipHostMalloc(&ctx->fb_pinned, sizeof(FbBlock) + sizeof(FbOut) + 256, hipHostMallocDefault) != hipSuccess)
       return ctx->fail(GHICP_ERR_HIP, "ghicp_clouds_recompute: pinned allocation failed");
   }
-  FbBlock* H = reinterpret_cast<FbBlock*>(ctx->fb_pinned);
-  FbOut* HO = reinterpret_cast<FbOut*>(reinterpret_cast<char*>(ctx->fb_pinned) + ((sizeof(FbBlock) + 63) / 64) * 64);
+  H = reinterpret_cast<FbBlock*>(ctx->fb_pinned);
+  HO = reinterpret_cast<FbOut*>(reinterpret_cast<char*>(ctx->fb_pinned) + ((sizeof(FbBlock) + 63) / 64) * 64);
   char* dblock;
   GH_TRY(ctx->reserve(B_FB_DESC, sizeof(FbBlock) + sizeof(FbOut) + 256, &dblock));
-  FbBlock* D = reinterpret_cast<FbBlock*>(dblock);
-  FbOut* O = reinterpret_cast<FbOut*>(dblock + ((sizeof(FbBlock) + 63) / 64) * 64);
+  D = reinterpret_cast<FbBlock*>(dblock);
+  O = reinterpret_cast<FbOut*>(dblock + ((sizeof(FbBlock) + 63) / 64) * 64);
   memset(H, 0, sizeof(FbBlock));
   H->nb = nb;
   for (int b = 0; b < nb; b++) {
@@ -667,24 +344,21 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
     H->c[b].xyz = xyz[b]; H->c[b].n = (int)n[b]; H->c[b].stride = stride;
     H->roff[b + 1] = H->roff[b] + (int)n[b];
   }
-  if (N == 0) return GHICP_OK;
-  auto upload = [&]() -> hipError_t { return hipMemcpyAsync(D, H, sizeof(FbBlock), hipMemcpyHostToDevice, s); };
-  auto report = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(HO, O, sizeof(FbOut), hipMemcpyDeviceToHost, s);
-    return e != hipSuccess ? e : hipStreamSynchronize(s);
-  };
+  return GHICP_OK;
+}
 
-  // ------------------------------------------------------------------ boxes of the raw clouds                          (sync 1)
+// ------------------------------------------------------------------ boxes of the raw clouds, voxel multipliers          (sync 1)
+int FbRun::raw_boxes() {
   GH_HIP(upload());
   hipLaunchKernelGGL(k_fb_bbox_init, dim3(cdiv(nb * 6, 256)), dim3(256), 0, s, O->bb, nb);
   hipLaunchKernelGGL(k_fb_bbox, dim3(64, nb), dim3(256), 0, s, (const FbBlock*)D, (const float*)nullptr, 0, O->bb);
   GH_HIP(report());
-  int ebmax = 1;
+  ebmax = 1;
   for (int b = 0; b < nb; b++) {
-    if (n[b] == 0) continue;
+    FbCloud& C = H->c[b];
+    if (C.n == 0) continue;
     float mm[6];
     decode_box(HO->bb + b * 6, mm);
-    FbCloud& C = H->c[b];
     C.vinv = 1.0f / cfg.voxel;  // filter.hpp:30
     unsigned long long maxv[3];
     for (int d = 0; d < 3; d++) {
@@ -698,18 +372,15 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
     if (total >= 18446744073709551615.0L) return ctx->fail(GHICP_ERR_CAPACITY, "voxel filter: the number of boxes exceeds the limit");  // filter.hpp:42-46
     ebmax = std::max(ebmax, bits_for((maxv[0] - 1) * C.mul_x + (maxv[1] - 1) * C.mul_y + (maxv[2] - 1)));
   }
-  const int cloud_bits = nb > 1 ? bits_for((unsigned long long)nb - 1) : 0;
-  if (ebmax + cloud_bits > 64) {  // no room for the cloud id above the voxel key
-    for (int i = 0; i < n_clouds; i++) GH_TRY(ghicp_cloud_recompute(clouds[i], xyz[i], n[i], stride));
-    return GHICP_OK;
-  }
+  cloud_bits = nb > 1 ? bits_for((unsigned long long)nb - 1) : 0;
+  return ebmax + cloud_bits > 64 ? FB_CLOUD_BY_CLOUD : GHICP_OK;  // no room for the cloud id above the voxel key
+}
 
-  // ------------------------------------------------------------------ voxel filter, down-sampled clouds, their boxes    (sync 2)
+// ------------------------------------------------------------------ voxel filter, down-sampled clouds, their boxes    (sync 2)
+int FbRun::voxel() {
   unsigned long long *vkeys, *vkeys2;
   unsigned *vvals, *vvals2;
-  unsigned char* flags;
-  int *headpos, *misc;
-  float4* dsg;
+  int* headpos;
   GH_TRY(ctx->reserve(B_GRID_KEYS, (size_t)N * 2 + 2, (unsigned**)&vkeys));
   GH_TRY(ctx->reserve(B_GRID_KEYS2, (size_t)N * 2 + 2, (unsigned**)&vkeys2));
   GH_TRY(ctx->reserve(B_GRID_VALS, (size_t)N + 1, &vvals));
@@ -744,14 +415,17 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   ctx->kt_end(KT_FB_VOXEL, kv1);
   GH_HIP(hipGetLastError());
   GH_HIP(report());
+  return GHICP_OK;
+}
+
+// ------------------------------------------------------------------ the three grids of every cloud, their cell bases   (host only)
+int FbRun::plan_grids(BscConst* BC) {
   const float r_pca = cfg.neighborhood_radius, r_nms = cfg.reg.radius_nonmax;
-  BscConst BC;
   float r_search = 0.f;
-  const bool bsc = cfg.reg.feature == GHICP_FEATURE_BSC, fpfh = cfg.reg.feature == GHICP_FEATURE_FPFH;
-  if (bsc) GH_TRY(gh_bsc_make_const(ctx, r_nms, cfg.reg.dof, cfg.pattern, &BC, &r_search));
-  unsigned long long t1 = 0, t2 = 0, t3 = 0;
+  if (bsc) GH_TRY(gh_bsc_make_const(ctx, r_nms, cfg.reg.dof, cfg.pattern, BC, &r_search));
+  t1 = t2 = t3 = 0;
   for (int b = 0; b <= nb; b++) { H->hoff[b] = HO->hoff[b]; H->moff[b] = HO->moff[b]; }
-  const int M = H->moff[nb];
+  M = H->moff[nb];
   for (int b = 0; b < nb; b++) {
     ghicp_cloud* c = clouds[b];
     c->m = H->moff[b + 1] - H->moff[b];
@@ -774,21 +448,15 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   }
   H->cb1[nb] = (unsigned)t1; H->cb2[nb] = (unsigned)t2; H->hb[nb] = (unsigned)t3;
   // the cell tables of all clouds are summed into one: when that gets large (clouds of large extent), halve the batch instead of
-  // failing -- whatever the cloud-by-cloud path handles must work here too (a single cloud is limited to 2^26 cells by gh_grid_desc)
-  auto split = [&]() -> int {
-    if (n_clouds == 1) return ghicp_cloud_recompute(clouds[0], xyz[0], n[0], stride);
-    const int half = n_clouds / 2;
-    GH_TRY(ghicp_clouds_recompute(ctx, half, clouds, xyz, n, stride));
-    return ghicp_clouds_recompute(ctx, n_clouds - half, clouds + half, xyz + half, n + half, stride);
-  };
+  // failing -- whatever the cloud-by-cloud path handles must work here too
   constexpr unsigned long long FB_CELL_BUDGET = 1ull << 28;  // 1 GB of cell table per grid
-  if (t1 >= FB_CELL_BUDGET || t2 >= FB_CELL_BUDGET || t3 >= FB_CELL_BUDGET) return split();
-  if (M <= 0) return GHICP_OK;
+  return (t1 >= FB_CELL_BUDGET || t2 >= FB_CELL_BUDGET || t3 >= FB_CELL_BUDGET) ? FB_HALVE : GHICP_OK;
+}
 
-  // ------------------------------------------------------------------ PCA grid, PCA, prune                              (sync 3)
+// ------------------------------------------------------------------ PCA grid, PCA, prune                              (sync 3)
+int FbRun::pca_prune() {
   float* lambda;
-  double* curv;
-  int *count, *cand;
+  int* count;
   unsigned* cells;
   GH_TRY(ctx->reserve(B_FE_LAMBDA, (size_t)M * 3 + 3, &lambda));
   GH_TRY(ctx->reserve(B_FE_CURV, (size_t)M + 1, &curv));
@@ -804,7 +472,7 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   GH_TRY(gh_unique_sorted_u32(ctx, keys1, M, cells, misc));  // the occupied cells, ascending (prims.hip)
   GH_HIP(hipMemsetAsync(misc + 4, 0, 8 * sizeof(int), s));
   ctx->kt_end(KT_FB_GRID, ku);
-  const float r2_pca = (float)((double)r_pca * (double)r_pca);  // pcl radiusSearch: static_cast<float>(radius*radius)
+  const float r_pca = cfg.neighborhood_radius, r2_pca = (float)((double)r_pca * (double)r_pca);  // pcl radiusSearch: static_cast<float>(radius*radius)
   hipEvent_t kt = ctx->kt_begin(KT_PCA);
   double* scat;
   GH_TRY(ctx->reserve(B_FE_SCATTER, (size_t)M * 6 + 6, &scat));
@@ -824,66 +492,12 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   GH_HIP(report());
   for (int b = 0; b <= nb; b++) H->coff[b] = HO->coff[b];
   for (int b = 0; b < nb; b++) clouds[b]->cand = H->coff[b + 1] - H->coff[b];
-  const int Ctot = H->coff[nb];
+  Ctot = H->coff[nb];
+  return GHICP_OK;
+}
 
-  // ------------------------------------------------------------------ NMS: candidate cells, decision rounds (sync 4), ranks
-  int* kpg = nullptr;
-  int Ktot = 0;
-  if (Ctot > 0) {
-    NmsrArgs A;
-    A.dsg = dsg; A.cand = cand; A.curv = curv; A.ctot = Ctot;
-    GH_TRY(ctx->reserve(B_NMSR_TABLE, (size_t)t3 + 4, &A.table));
-    GH_TRY(ctx->reserve(B_NMSR_HEAD, (size_t)Ctot + 1, &A.upos));
-    GH_TRY(ctx->reserve(B_NMSR_CELL, (size_t)Ctot + 1, &A.ccell));
-    GH_TRY(ctx->reserve(B_NMSR_KEY, (size_t)Ctot + 1, &A.ckey));
-    GH_TRY(ctx->reserve(B_NMSR_PTS, (size_t)Ctot + 1, &A.spts));
-    GH_TRY(ctx->reserve(B_NMSR_SKEY, (size_t)Ctot + 1, &A.skey));
-    GH_TRY(ctx->reserve(B_NMSR_PTS0, (size_t)Ctot + 1, &A.spts0));
-    GH_TRY(ctx->reserve(B_NMSR_SKEY0, (size_t)Ctot + 1, &A.skey0));
-    GH_TRY(ctx->reserve(B_NMSR_STATE, (size_t)Ctot * 2 + 32, &A.state));
-    A.urun = A.state + (((size_t)Ctot + 15) & ~(size_t)15);
-    GH_TRY(ctx->reserve(B_NMSR_NEXT, (size_t)Ctot * 2 + 2, &A.blk));
-    A.next = A.blk + Ctot + 1;
-    GH_TRY(ctx->reserve(B_NMSR_LIST, (size_t)t3 + 2, &A.head));
-    GH_TRY(ctx->reserve(B_NMSR_SEL, (size_t)Ctot + 1, &A.sel));
-    GH_TRY(ctx->reserve(B_FE_KP, (size_t)Ctot + 1, &kpg));
-    A.kcount = O->kcount;
-    A.undecided = O->nms_und;
-    GH_HIP(upload());  // g3 / hb (the device wrote coff itself)
-    hipEvent_t kr = ctx->kt_begin(KT_FB_RANK);
-    GH_HIP(hipMemsetAsync(A.table, 0, ((size_t)t3 + 2) * sizeof(unsigned), s));
-    GH_HIP(hipMemsetAsync(A.head, 0xff, (size_t)t3 * sizeof(int), s));
-    GH_HIP(hipMemsetAsync(O->kcount, 0, sizeof(int) * FB_MAX, s));
-    hipLaunchKernelGGL(k_fb_nmsr_keys, dim3(cdiv(Ctot, 256)), dim3(256), 0, s, (const FbBlock*)D, A);
-    GH_TRY(gh_scan_inclusive_u32(ctx, A.table + 1, (long long)t3));
-    hipLaunchKernelGGL(k_fb_nmsr_fill, dim3(cdiv(Ctot, 256)), dim3(256), 0, s, A, (unsigned)t3);
-    hipLaunchKernelGGL(k_fb_nmsr_sort, dim3(cdiv(Ctot, 256)), dim3(256), 0, s, A);
-    ctx->kt_end(KT_FB_RANK, kr);
-    const float r2_nms = (float)((double)r_nms * (double)r_nms);
-    for (int seq = 0;; seq++) {
-      hipEvent_t kn = ctx->kt_begin(KT_NMS_ROUND);
-      GH_HIP(hipMemsetAsync(O->nms_und, 0, sizeof(int) * FB_NMS_ROUNDS, s));
-      for (int r = 0; r < FB_NMS_ROUNDS; r++)
-        hipLaunchKernelGGL(k_fb_nmsr_round, dim3(cdiv(Ctot, 256)), dim3(256), 0, s, (const FbBlock*)D, A, r2_nms, r, (seq == 0 && r == 0) ? 1 : 0);
-      ctx->kt_end(KT_NMS_ROUND, kn);
-      GH_HIP(hipGetLastError());
-      GH_HIP(report());
-      if (HO->nms_und[FB_NMS_ROUNDS - 1] == 0) break;  // every candidate has decided
-      if (seq > 4096) return ctx->fail(GHICP_ERR_INTERNAL, "ghicp_clouds_recompute: the NMS rounds do not terminate");  // (each sequence decides at least one candidate)
-    }
-    for (int b = 0; b < nb; b++) {
-      clouds[b]->k = HO->kcount[b];
-      H->koff[b + 1] = H->koff[b] + HO->kcount[b];
-    }
-    Ktot = H->koff[nb];
-    if (Ktot > 0) {
-      hipEvent_t kk = ctx->kt_begin(KT_NMS_ROUND);
-      hipLaunchKernelGGL(k_fb_nmsr_rank, dim3(nb, 8), dim3(256), 0, s, (const FbBlock*)D, A, kpg);
-      ctx->kt_end(KT_NMS_ROUND, kk);
-    }
-  }
-
-  // ------------------------------------------------------------------ outputs into the handles, BSC                     (sync 6)
+// ------------------------------------------------------------------ outputs into the handles
+int FbRun::outputs() {
   for (int b = 0; b < nb; b++) {
     ghicp_cloud* c = clouds[b];
     GH_HIP(c->ds.reserve(((size_t)c->m + 1) * sizeof(float4)));
@@ -896,35 +510,69 @@ extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cl
   GH_HIP(upload());
   hipEvent_t ko = ctx->kt_begin(KT_FB_OUT);
   hipLaunchKernelGGL(k_fb_copy_ds, dim3(cdiv(M, 256)), dim3(256), 0, s, (const FbBlock*)D, (const float4*)dsg, M);
+  lcs = nullptr;
   if (Ktot > 0) {
-    float* lcs = nullptr;
     if (bsc) GH_TRY(ctx->reserve(B_P_LCS, (size_t)Ktot * 12 + 12, &lcs));
     hipLaunchKernelGGL(k_fb_keypoints_out, dim3(cdiv(Ktot, 256)), dim3(256), 0, s, (const FbBlock*)D, (const float4*)dsg, (const int*)kpg, Ktot, lcs);
     if (bsc) hipLaunchKernelGGL(k_fb_zero_feat, dim3(cdiv((long long)Ktot * 56, 256)), dim3(256), 0, s, (const FbBlock*)D, Ktot);
-    ctx->kt_end(KT_FB_OUT, ko);
-    ko = nullptr;
-    if (bsc) {
-      const float4* pts2;
-      const unsigned *start2, *keys2;
-      const GridSlots sl2 = {B_GRID2_KEYS, B_GRID2_KEYS2, B_GRID2_VALS, B_GRID2_VALS2, B_GRID2_START, B_GRID2_PTS};
-      GH_TRY(build_grid(ctx, D, 1, dsg, M, (unsigned)t2, sl2, &pts2, &start2, &keys2));
-      hipEvent_t kb = ctx->kt_begin(KT_BSC);
-      hipLaunchKernelGGL(k_fb_bsc, dim3((unsigned)Ktot), dim3(BT), 0, s, (const FbBlock*)D, pts2, start2, BC, lcs);
-      ctx->kt_end(KT_BSC, kb);
-    }
   }
-  if (ko) ctx->kt_end(KT_FB_OUT, ko);
-  if (fpfh && Ktot > 0) {  // compute_fpfh_feature over ALL down-sampled points, then the keypoints' rows (main:122-127)
+  ctx->kt_end(KT_FB_OUT, ko);
+  return GHICP_OK;
+}
+
+// ------------------------------------------------------------------ feature grid; BSC strings or FPFH rows            (last sync)
+int FbRun::features(const BscConst& BC) {
+  if (Ktot > 0 && (bsc || fpfh)) {
     const float4* pts2;
     const unsigned *start2, *keys2;
     const GridSlots sl2 = {B_GRID2_KEYS, B_GRID2_KEYS2, B_GRID2_VALS, B_GRID2_VALS2, B_GRID2_START, B_GRID2_PTS};
     GH_TRY(build_grid(ctx, D, 1, dsg, M, (unsigned)t2, sl2, &pts2, &start2, &keys2));
-    float* hist;
-    GH_TRY(ctx->reserve(B_P_FEAT_S, (size_t)M * 33 * sizeof(float) + 64, (char**)&hist));
-    GH_TRY(gh_fpfh_batch_dev(ctx, dsg, M, pts2, start2, D->g2, D->cb2, D->moff, nb, hist));
-    hipLaunchKernelGGL(k_fb_gather_rows33, dim3(cdiv((long long)Ktot * 33, 256)), dim3(256), 0, s, (const FbBlock*)D, (const float*)hist, Ktot);
+    if (bsc) {
+      hipEvent_t kb = ctx->kt_begin(KT_BSC);
+      hipLaunchKernelGGL(k_fb_bsc, dim3((unsigned)Ktot), dim3(BT), 0, s, (const FbBlock*)D, pts2, start2, BC, lcs);
+      ctx->kt_end(KT_BSC, kb);
+    } else {  // compute_fpfh_feature over ALL down-sampled points, then the keypoints' rows (main:122-127)
+      float* hist;
+      GH_TRY(ctx->reserve(B_P_FEAT_S, (size_t)M * 33 * sizeof(float) + 64, (char**)&hist));
+      GH_TRY(gh_fpfh_batch_dev(ctx, dsg, M, pts2, start2, D->g2, D->cb2, D->moff, nb, hist));
+      hipLaunchKernelGGL(k_fb_gather_rows33, dim3(cdiv((long long)Ktot * 33, 256)), dim3(256), 0, s, (const FbBlock*)D, (const float*)hist, Ktot);
+    }
   }
   GH_HIP(hipGetLastError());
   GH_HIP(hipStreamSynchronize(s));
   return GHICP_OK;
+}
+
+// Front ends of n_clouds raw clouds (device pointers xyz[i], n[i] points of `stride` floats) into existing handles of ONE front-end
+// configuration and one context.  Equivalent to ghicp_cloud_recompute(clouds[i], xyz[i], n[i], stride) for every i, bit for bit.
+extern "C" int ghicp_clouds_recompute(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cloud* const* clouds, const float* const* xyz, const int64_t* n, int stride) {
+  GH_ENTER(ctx);
+  GH_ARG(n_clouds >= 0 && (n_clouds == 0 || (clouds != nullptr && xyz != nullptr && n != nullptr)) && stride >= 3);
+  if (n_clouds == 0) return GHICP_OK;
+  FbRun R;
+  R.ctx = ctx; R.s = ctx->stream; R.nb = n_clouds; R.clouds = clouds; R.N = 0;
+  for (int i = 0; i < n_clouds; i++) {
+    GH_ARG(clouds[i] != nullptr && clouds[i]->ctx == ctx && n[i] >= 0 && n[i] < (1ll << 31) - 2);
+    if (!same_front_end(clouds[i]->cfg, clouds[0]->cfg))
+      return ctx->fail(GHICP_ERR_ARG, "ghicp_clouds_recompute: cloud %d has a different front-end configuration", i);
+    for (int j = 0; j < i; j++) GH_ARG(clouds[j] != clouds[i]);
+    R.N += n[i];
+  }
+  R.cfg = clouds[0]->cfg; R.bsc = R.cfg.reg.feature == GHICP_FEATURE_BSC; R.fpfh = R.cfg.reg.feature == GHICP_FEATURE_FPFH;
+  // what the batch does not cover goes cloud by cloud: no down-sampling, host pointers
+  if (!(R.cfg.voxel > 0.f) || ctx->host_ptrs) return fb_cloud_by_cloud(n_clouds, clouds, xyz, n, stride);
+  if (n_clouds > FB_MAX || R.N + n_clouds >= (1ll << 31) - 2) return fb_halve(ctx, n_clouds, clouds, xyz, n, stride);
+  GH_TRY(R.begin(xyz, n, stride));
+  if (R.N == 0) return GHICP_OK;
+  BscConst BC;
+  int rc = R.raw_boxes();
+  if (rc == GHICP_OK) rc = R.voxel();
+  if (rc == GHICP_OK) rc = R.plan_grids(&BC);
+  if (rc == FB_CLOUD_BY_CLOUD) return fb_cloud_by_cloud(n_clouds, clouds, xyz, n, stride);
+  if (rc == FB_HALVE) return fb_halve(ctx, n_clouds, clouds, xyz, n, stride);
+  if (rc != GHICP_OK || R.M <= 0) return rc;
+  GH_TRY(R.pca_prune());
+  GH_TRY(R.nms());
+  GH_TRY(R.outputs());
+  return R.features(BC);
 }

@@ -9,7 +9,7 @@
 //   tail     cell depth / normalised weight, per-plane pair statistics, 441-bit string + the flip
 //            variants with their "294-cell" quirk                                            (bfe:333-372, 464-565, 678-837)
 // Wavefront shuffle reductions carry the 4 + 6 f64 sums of sweeps A/B.
-#include "grid.h"
+#include "frontend.h"
 #include "devmath.h"
 #include "bsc_dev.h"
 

@@ -1,4 +1,4 @@
-// Internal: the per-cloud front-end cache handle (cloud.hip) -- shared with the batched front end (batch.hip).
+// Internal: the per-cloud front-end cache handle (cloud.hip) -- shared with the batched front end (batch.hip, batch_dev.h).
 #pragma once
 #include "grid.h"
 

@@ -56,11 +56,8 @@ struct DevBuf {
 };
 
 enum BufSlot {
-  // staging (host-pointer mode)
-  B_STAGE0 = 0, B_STAGE1, B_STAGE2, B_STAGE3, B_STAGE4, B_STAGE5, B_STAGE6, B_STAGE7,
   // loop
-  B_LOOP_STATE, B_LOOP_KPS, B_LOOP_PARTMIN, B_LOOP_PARTIDX, B_LOOP_PARTSUM, B_LOOP_PARTMIN2, B_LOOP_PARTIDX2, B_LOOP_FDT,
-  B_LOOP_SP, B_LOOP_TP, B_LOOP_TRACE, B_LOOP_WFD, B_LOOP_KMW, B_LOOP_KMMATCH, B_LOOP_KMSCR, B_LOOP_ACC,
+  B_LOOP_STATE = 0, B_LOOP_SP, B_LOOP_KMW, B_LOOP_KMSCR,
   // spatial grid / sort
   B_GRID_KEYS, B_GRID_KEYS2, B_GRID_VALS, B_GRID_VALS2, B_GRID_TMP, B_GRID_START, B_GRID_PTS, B_GRID_MISC,
   B_GRID2_KEYS, B_GRID2_KEYS2, B_GRID2_VALS, B_GRID2_VALS2, B_GRID2_START, B_GRID2_PTS,
@@ -71,14 +68,14 @@ enum BufSlot {
   B_P_KEEP_S, B_P_KEEP_T, B_P_DS_S, B_P_DS_T, B_P_KP_S, B_P_KP_T, B_P_KPXYZ_S, B_P_KPXYZ_T, B_P_FEAT_S, B_P_FEAT_T, B_P_LCS,
   B_P_FD, B_P_MISC, B_P_PATTERN, B_FD_JOBS, B_TRANSFORM_JOBS,
   B_KM_LX, B_KM_MISC, B_KM_SLACK, B_KM_LSTAT, B_KM_ORDER, B_KM_MASK,
-  // batched front end (batch.hip)
-  B_FB_DESC, B_FB_HEADPOS, B_FB_DS, B_FB_ORD,
-  // hand-written scan / select primitives (prims.hip): tile totals; round-based NMS of the batched front end (batch.hip)
-  B_PRIM_TMP, B_NMSR_KEY, B_NMSR_CELL, B_NMSR_TABLE, B_NMSR_HEAD, B_NMSR_PTS, B_NMSR_SKEY, B_NMSR_STATE, B_NMSR_NEXT, B_NMSR_SEL, B_NMSR_MISC, B_NMSR_LIST, B_NMSR_PTS0, B_NMSR_SKEY0,
+  // batched front end (batch.hip): descriptor block and report, positions of the voxel run heads, concatenated down-sampled clouds
+  B_FB_DESC, B_FB_HEADPOS, B_FB_DS,
+  // hand-written scan / select primitives (prims.hip): tile totals; round-based NMS of the batched front end (batch_nms.hip)
+  B_PRIM_TMP, B_NMSR_KEY, B_NMSR_CELL, B_NMSR_TABLE, B_NMSR_HEAD, B_NMSR_PTS, B_NMSR_SKEY, B_NMSR_STATE, B_NMSR_NEXT, B_NMSR_SEL, B_NMSR_LIST, B_NMSR_PTS0, B_NMSR_SKEY0,
   // fine registration (icp.hip): coarse target grid, source grids (reciprocal), per-point state
   B_ICP_TC_KEYS, B_ICP_TC_KEYS2, B_ICP_TC_VALS, B_ICP_TC_VALS2, B_ICP_TC_START, B_ICP_TC_PTS,
   B_ICP_SC_KEYS, B_ICP_SC_KEYS2, B_ICP_SC_VALS, B_ICP_SC_VALS2, B_ICP_SC_START, B_ICP_SC_PTS,
-  B_ICP_CUR, B_ICP_Q, B_ICP_NN, B_ICP_ND, B_ICP_NN2, B_ICP_ND2, B_ICP_KEYS, B_ICP_KEYS2, B_ICP_SORTTMP, B_ICP_PART, B_ICP_STATE,
+  B_ICP_CUR, B_ICP_Q, B_ICP_NN, B_ICP_ND, B_ICP_NN2, B_ICP_ND2, B_ICP_KEYS, B_ICP_PART, B_ICP_STATE,
   B_ICP_PEND, B_ICP_TNRM, B_ICP_OUT,
   // generalized ICP (icp.hip): covariances of both clouds, per-correspondence Mahalanobis matrices, the packed source
   B_GICP_COVS, B_GICP_COVT, B_GICP_MAHAL, B_GICP_SRC4,
@@ -91,7 +88,7 @@ enum BufSlot {
 };
 
 enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_FD_BSC, KT_NMS_ROUND, KT_VOXEL_SORT,
-              KT_FB_VOXEL, KT_FB_GRID, KT_FB_PRUNE, KT_FB_RANK, KT_FB_OUT,  // stages of the batched front end (batch.hip) around the kernels above
+              KT_FB_VOXEL, KT_FB_GRID, KT_FB_PRUNE, KT_FB_RANK, KT_FB_OUT,  // stages of the batched front end (batch.hip, batch_nms.hip) around the kernels above
               KT_PAIR_LOOP,                                                  // the persistent pair loop (pair_loop.hip): all classes of a batch, fork -> join
               KT_TRANSFORM,                                                  // S7 of a batch (ghicp_transform_clouds)
               KT_PAIR_LOOP_DISPATCH,                                         // ONE k_pair_loop dispatch (a class launch of a batch), timed on the stream it runs on -- what rocprofv3's kernel trace reports per row

@@ -14,7 +14,7 @@
 //               result is bit-identical to the scalar loop (an MFMA GEMM of z-scored rows would
 //               re-associate the sums).
 // Both are HBM-write-bound: 56(V ks + kt) resp. 132(ks + kt) bytes in, 2 (x 2 with the transposed copy) resp. 4 bytes per pair out.
-#include "ctx.h"
+#include "frontend.h"
 
 namespace {
 

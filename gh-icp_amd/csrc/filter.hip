@@ -7,10 +7,8 @@
 //   k_sor_partials  (sum, sum of squares) of every tile of SOR_TILE consecutive distances, in index order (N9); the tiles are added in index
 //                   order on the host, which also takes the square root -- the threshold is the restatement's bit for bit
 //   flag kernels    one byte per point, compacted by the library's own select (prims.hip)
-#include "grid.h"
+#include "frontend.h"
 #include "prims.h"
-
-float gh_fpfh_cell(const float* mm, long long m);  // fpfh.hip: the cell size of the k-NN grid of one cloud
 
 namespace {
 

@@ -8,7 +8,7 @@
 //   k_spfh      Darboux-frame pair features -> 3 x 11 bins, increment 100/(k-1) (computePointSPFHSignature)
 //   k_fpfh      sum_{d2 != 0} SPFH(neighbour) / d2, each 11-bin block rescaled to 100 (weightPointSPFHSignature)
 // HBM-bound by contract (16 B in + 132 B out per point); the neighbour lists (160 B/point) stay L2-resident.
-#include "grid.h"
+#include "frontend.h"
 #include "devmath.h"
 
 namespace {
@@ -279,8 +279,6 @@ __global__ __launch_bounds__(256) void k_gather_rows33(const float* __restrict__
 }
 
 }  // namespace
-
-float gh_fpfh_cell(const float* mm, long long m);
 
 int gh_fpfh_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, float* normals_opt, float* hist) {
   if (m <= 0) return GHICP_OK;

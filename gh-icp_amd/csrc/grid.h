@@ -57,6 +57,12 @@ inline GridDesc gh_grid_desc(const float* mm, long long n, float cell) {
   return g;
 }
 
+inline int bits_for(unsigned long long maxv) {  // bits of a radix sort over keys 0 .. maxv
+  int b = 1;
+  while (b < 64 && (maxv >> b) != 0ull) b++;
+  return b;
+}
+
 struct GridSlots {
   BufSlot keys, keys2, vals, vals2, start, pts;
 };

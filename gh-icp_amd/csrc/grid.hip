@@ -1,7 +1,7 @@
 // Uniform-grid build (cell keys -> stable radix sort -> cell table -> points in cell order) and the
 // voxel down-sampling filter.  The sort, scan and select primitives are this library's own (prims.hip); rounds 1-5 called rocPRIM's
 // Onesweep here (with its merge-sort limit lowered to 4096 items: the default dispatch cost ~17 launches per sort below 1 M items).
-#include "grid.h"
+#include "frontend.h"
 #include "prims.h"
 
 #include <algorithm>
@@ -76,12 +76,6 @@ __global__ __launch_bounds__(256) void k_gather_sorted(const float* __restrict__
   if (i >= n) return;
   const long long s = vals[i];
   pts[i] = make_float4(xyz[s * stride], xyz[s * stride + 1], xyz[s * stride + 2], __uint_as_float((unsigned)s));
-}
-
-static int bits_for(unsigned long long maxv) {
-  int b = 1;
-  while (b < 64 && (maxv >> b) != 0ull) b++;
-  return b;
 }
 
 }  // namespace

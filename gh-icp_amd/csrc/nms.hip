@@ -7,10 +7,10 @@
 // order is the unique fixed point of
 //     selected(i)  <=>  no selected j with rank(j) < rank(i) and d2(i,j) < R^2          
 // and is computed in two ways: here by ONE workgroup per cloud that sweeps the rank-ordered candidates in chunks (nms_dev.h: ghicp_nms,
-// ghicp_keypoints, the pair API, ghicp_cloud_recompute), and in batch.hip by decision rounds with one thread per candidate over every cloud
+// ghicp_keypoints, the pair API, ghicp_cloud_recompute), and in batch_nms.hip by decision rounds with one thread per candidate over every cloud
 // of a batch at once (k_fb_nmsr_*: ghicp_clouds_recompute).  Same keypoints in the same order either way (tests/test_gpu_nms.py).
 // Rank = (curvature desc, candidate order asc): stable radix sort, so ties resolve to the lower point index.
-#include "grid.h"
+#include "frontend.h"
 
 #include <algorithm>
 

@@ -1,5 +1,5 @@
 // Greedy non-maximum suppression of ONE cloud's rank-ordered candidates by one 256-thread workgroup (keypoint_detect.hpp:149-191);
-// shared by the single-cloud kernel (nms.hip) and the batched front end (batch.hip).
+// the single-cloud kernel of nms.hip (the batched front end decides in rounds instead: batch_nms.hip).
 #pragma once
 #include "grid.h"
 #include "devmath.h"

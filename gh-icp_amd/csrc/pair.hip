@@ -3,19 +3,7 @@
 // -> keypoint coordinates as f64 (DataIo::savecoordinates, dataio.hpp:609-627) -> BSC (target dof 0,
 // source reg_dof) -> feature distance -> GHRegistration::ghicp_reg.  Every stage is the public ABI
 // function of the same name; nothing leaves HBM between stages except element counts.
-#include "ctx.h"
-
-int gh_voxel_filter_dev(ghicp_ctx* ctx, const float* xyz, long long n, int stride, float voxel, int32_t* keep, long long* m_out);
-int gh_keypoints_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, float radius, float ratio_max, int min_n, float nms_radius,
-                     int32_t* kp, long long* k_out);
-int gh_bsc_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, const int32_t* kp, long long K, float R, int dof, const int32_t* pattern_host,
-               uint8_t* feat, float* lcs);
-int gh_bbox_dev(ghicp_ctx* ctx, const float* xyz, long long n, int stride, float* mm_host6);
-int gh_fpfh_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, float* normals_opt, float* hist);
-int gh_gather_rows33_dev(ghicp_ctx* ctx, const float* hist, const int32_t* idx, long long k, float* out);
-int gh_fd_fpfh_dev(ghicp_ctx* ctx, const float* histS, int ks, const float* histT, int kt, float* FD);
-int gh_register_pairs_batched(ghicp_ctx* ctx, const ghicp_pair_config* cfg, int32_t n_pairs, const float* const* xyzS, const int64_t* nS,
-                              const float* const* xyzT, const int64_t* nT, int stride, ghicp_pair_stats* stats, int* handled);  // cloud.hip
+#include "frontend.h"
 
 namespace {
 

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(PT) void k_scan_apply(unsigned* __restrict__ data, 
   unsigned v[PI];
   unsigned acc = 0;
   // 64 bytes per thread as four 16-byte accesses -- only when the thread's range lies inside n AND starts on a 16-byte boundary: t0 is a multiple
-  // of 16 items, so that is a property of `data` alone (uniform over the launch).  A base that is merely 4-byte aligned (batch.hip scans
+  // of 16 items, so that is a property of `data` alone (uniform over the launch).  A base that is merely 4-byte aligned (batch_nms.hip scans
   // `table + 1`) takes the item-wise path, like the thread that straddles n.
   const bool whole = t0 + PI <= n && (reinterpret_cast<uintptr_t>(data) & 15u) == 0;
   if (whole) {

@@ -1,5 +1,5 @@
 #!/bin/bash
-# ISA of one kernel of one translation unit (development aid): scripts/isa.sh batch.hip k_fb_pca_cells [out.s]
+# ISA of one kernel of one translation unit (development aid): scripts/isa.sh batch.hip k_fb_pca_cells [out.s]   (k_fb_nmsr_*: batch_nms.hip)
 # prints instruction count, VGPRs, scratch; writes the kernel's ISA to out.s (default /tmp/<kernel>.s)
 src=$1; k=$2; out=${3:-/tmp/$k.s}
 cd "$(dirname "$0")/../gh-icp_amd/csrc" || exit 1

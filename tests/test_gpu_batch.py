@@ -1,4 +1,4 @@
-"""Batched front end (gh-icp_amd/csrc/batch.hip): ghicp_clouds_recompute must reproduce ghicp_cloud_recompute cloud by cloud, bit for
+"""Batched front end (gh-icp_amd/csrc/batch.hip, its NMS rounds: batch_nms.hip): ghicp_clouds_recompute must reproduce ghicp_cloud_recompute cloud by cloud, bit for
 bit -- down-sampled points, keypoint ids and coordinates, BSC strings -- for batches of different clouds, including empty ones, and the
 registrations that follow must be identical."""
 import numpy as np
@@ -122,5 +122,28 @@ def test_batch_large_extent_splits_instead_of_failing(ctx, api, synth):
     ctx.clouds_recompute(batch, raws)
     for c, d in zip(single, batch):
         _same(c, d)
+    for c in single + batch:
+        c.close()
+
+
+def test_batch_of_more_than_64_clouds(ctx, api, synth):
+    """More clouds than a batch holds (FB_MAX = 64): the call halves itself, 70 -> 35 + 35, and every handle still equals its cloud-by-cloud twin.
+    The clouds are the 70 azimuth sectors of one scan, 500 points each, one of them emptied and one cut to a single point: the smallest size (in
+    steps of 100) at which ten clouds have keypoints -- 15 do, 9 at 400 points (the first 500 ROWS of a scan are sparse rings without any)."""
+    P = 500
+    cfg = api.pair_config(api.FEATURE_BSC, api.CORR_NN, dof=6, voxel=0.2, pattern=synth.bsc_pattern_glibc(), max_iter=40)
+    scan = synth.tls_pair(70 * P, pair_id=26).source
+    scan = scan[np.argsort(np.arctan2(scan[:, 1], scan[:, 0]), kind="stable")]
+    raws = [np.ascontiguousarray(scan[i * P:(i + 1) * P]) for i in range(70)]
+    raws[3], raws[40] = raws[3][:0], raws[40][:1]
+    single = [ctx.cloud_create(cfg, scan[:300]) for _ in raws]
+    batch = [ctx.cloud_create(cfg, scan[:300]) for _ in raws]
+    for c, r in zip(single, raws):
+        c.recompute(r)
+    ctx.clouds_recompute(batch, raws)
+    for c, d in zip(single, batch):
+        _same(c, d)
+    assert (batch[3].info().m, batch[40].info().m) == (0, 1)
+    assert sum(c.info().k > 0 for c in batch) >= 10  # the comparison is not vacuous
     for c in single + batch:
         c.close()

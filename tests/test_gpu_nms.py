@@ -3,7 +3,7 @@
 Part A drives the one-workgroup sweep (gh_nms_greedy_cloud of nms_dev.h, through ghicp_nms) with hand-built candidates whose rank is known:
 counts around a wave and a chunk, a suppressor in the same wave / the next wave / the next chunk, the crossing from the LDS list to the
 global grid at NMS_SEL_CAP selected keypoints, the column cap NMS_COL_CAP, the widening and coarsening branches of gh_grid_desc, a
-distance exactly at R, plateaus of equal curvature and odd keys.  Part B drives the batched decision rounds (k_fb_nmsr_* of batch.hip,
+distance exactly at R, plateaus of equal curvature and odd keys.  Part B drives the batched decision rounds (k_fb_nmsr_* of batch_nms.hip,
 through ghicp_clouds_recompute) with lattice "ribbons" whose PCA curvature forms long chains of decisions or long plateaus.
 
 Two CPU references must agree with each other before the GPU is asked: the oracle (oracle.nms / oracle.keypoints) and the plain greedy
@@ -75,7 +75,7 @@ def grid_desc(pts, radius):
 def test_the_caps_are_what_the_fixtures_were_built_for():
     """The regime asserts below use the constants of this file: a changed cap must fail here, loudly, not move a fixture into another regime."""
     src = os.path.join(ROOT, "gh-icp_amd", "csrc")
-    dev, batch = open(os.path.join(src, "nms_dev.h")).read(), open(os.path.join(src, "batch.hip")).read()
+    dev, batch = open(os.path.join(src, "nms_dev.h")).read(), open(os.path.join(src, "batch_dev.h")).read() + open(os.path.join(src, "batch_nms.hip")).read()
     for text, name, want in ((dev, "NMS_T", NMS_T), (dev, "NMS_SEL_CAP", NMS_SEL_CAP), (dev, "NMS_COL_CAP", NMS_COL_CAP), (batch, "FB_NMS_ROUNDS", FB_NMS_ROUNDS)):
         m = re.search(r"constexpr int %s = (\d+);" % name, text)
         assert m and int(m.group(1)) == want, name
@@ -483,7 +483,7 @@ def _reference(oracle, raw, radius_nonmax=R):
 
 
 def sync_depth(ds, curv, cand, radius):
-    """Rounds the fixed-point rule of batch.hip needs when every round sees only the decisions of the rounds before it:
+    """Rounds the fixed-point rule of batch_nms.hip needs when every round sees only the decisions of the rounds before it:
     suppressed(i) <=> a neighbour of higher rank is selected, selected(i) <=> every neighbour of higher rank is suppressed."""
     from scipy.spatial import cKDTree
 

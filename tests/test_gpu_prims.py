@@ -79,7 +79,7 @@ def scan_inputs(rng, n):
 
 def test_scan_at_every_size_base_offset_and_value_pattern(ctx):
     """ghicp_scan_inclusive_u32 in place on a window that starts 0, 1, 2 or 3 words past a 256-byte boundary (k_scan_apply's 16-byte path
-    may be taken for the first of these only; batch.hip scans `table + 1`).  Every size >= 17 has threads whose 16 items lie inside n and,
+    may be taken for the first of these only; batch_nms.hip scans `table + 1`).  Every size >= 17 has threads whose 16 items lie inside n and,
     unless n is a multiple of 16, one thread that straddles n."""
     rng = np.random.default_rng(11)
     for n in SIZES:

@@ -80,7 +80,7 @@ def test_solver_fuzz_in_reverse_lane_order():
 
 def test_batched_nms_rounds_in_reverse_lane_order():
     """The batched NMS tests (Part B of tests/test_gpu_nms.py) with the interpreter running waves and lanes in REVERSE order: the decision
-    rounds of batch.hip claim that any order of decisions gives the same keypoints -- chains, plateaus, rank tiles, offsets inside a batch."""
+    rounds of batch_nms.hip claim that any order of decisions gives the same keypoints -- chains, plateaus, rank tiles, offsets inside a batch."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from hipsim import build
 
