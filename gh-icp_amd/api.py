@@ -53,9 +53,9 @@ EXPORTS = [
     "ghicp_rigid_svd", "ghicp_rigid_svd_host", "ghicp_register", "ghicp_loop_create", "ghicp_iterate", "ghicp_loop_result", "ghicp_loop_destroy", "ghicp_transform_cloud", "ghicp_transform_clouds", "ghicp_register_pair",
     "ghicp_register_pairs",
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
-    "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_covariances",
+    "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
-    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
+    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
     "ghicp_pairqueue_barrier", "ghicp_pairqueue_static_share", "ghicp_pairqueue_claim", "ghicp_pairqueue_counter_reset",
     "ghicp_pairqueue_gather_records", "ghicp_pairqueue_pack_records", "ghicp_pairqueue_register_pairs",
@@ -118,6 +118,11 @@ class IcpStats(C.Structure):
 class RefineResult(C.Structure):
     """ghicp_refine_result: one pair of ghicp_refine_clouds."""
     _fields_ = [("T_icp", C.c_float * 16), ("Rt_refined", C.c_double * 16), ("stats", IcpStats)]
+
+
+class GicpResult(C.Structure):
+    """ghicp_gicp_result: one pair of ghicp_gicp_clouds."""
+    _fields_ = [("T", C.c_float * 16), ("stats", IcpStats)]
 
 
 def icp_params(max_iter=50, reciprocal=False, trimmed=False, metric=ICP_POINT_TO_POINT, thre_dis=0.5, min_overlap=0.1,
@@ -645,15 +650,21 @@ class Context:
         d.update(T=T.reshape(4, 4), transformed=out)
         return d
 
-    def gicp(self, xyzS, xyzT, params: GicpParams, want_transformed=True):
-        """gicp_reg.  Returns the dict of icp(): done, T (4,4) f32, transformed tensor, + ghicp_icp_stats fields."""
+    def gicp(self, xyzS, xyzT, params: GicpParams, want_transformed=True, guess=None):
+        """gicp_reg.  Returns the dict of icp(): done, T (4,4) f32, transformed tensor, + ghicp_icp_stats fields.  guess: (4,4) initial
+        source->target pose (ghicp_gicp_from; T is then the total pose, guess included); None: ghicp_gicp."""
         t = self.torch
         xS, xT = self._xyz(xyzS), self._xyz(xyzT)
         T = np.zeros(16, np.float32)
         out = t.empty((xS.shape[0], 3), dtype=t.float32, device=self.dev) if want_transformed else None
         st = IcpStats()
-        self._check(self.lib.ghicp_gicp(self.h, _ptr(xS), C.c_int64(xS.shape[0]), xS.shape[1], _ptr(xT), C.c_int64(xT.shape[0]), xT.shape[1],
-                                        C.byref(params), T.ctypes.data_as(C.POINTER(C.c_float)), _ptr(out), C.byref(st)))
+        head = (self.h, _ptr(xS), C.c_int64(xS.shape[0]), xS.shape[1], _ptr(xT), C.c_int64(xT.shape[0]), xT.shape[1], C.byref(params))
+        tail = (T.ctypes.data_as(C.POINTER(C.c_float)), _ptr(out), C.byref(st))
+        if guess is None:
+            self._check(self.lib.ghicp_gicp(*head, *tail))
+        else:
+            g = np.ascontiguousarray(guess, dtype=np.float32).reshape(16)
+            self._check(self.lib.ghicp_gicp_from(*head, g.ctypes.data_as(C.POINTER(C.c_float)), *tail))
         d = {k: getattr(st, k) for k, _ in IcpStats._fields_ if k != "pad_"}
         d.update(T=T.reshape(4, 4), transformed=out)
         return d
@@ -747,6 +758,12 @@ class Cloud:
         self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_refine(self.h, int(k)))
         return self
 
+    def prepare_gicp(self, k=20, eps=1e-3):
+        """What the cloud needs to serve as source or target of Context.gicp_clouds: its covariances for (k, eps) and its 1-NN grids.
+        Needed again after every recompute."""
+        self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_gicp(self.h, int(k), C.c_double(eps)))
+        return self
+
     def close(self):
         if self.h:
             self.ctx.lib.ghicp_cloud_destroy(self.h)
@@ -827,7 +844,33 @@ def _refine_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
     return out
 
 
+def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
+    """ghicp_gicp_clouds: generalized ICP of the down-sampled clouds of every (Cloud S, Cloud T) from Rt_init (n x 4 x 4 f64; None: identity)
+    in one launch sequence per outer iteration.  Both clouds of every pair must have been through Cloud.prepare_gicp with the parameters'
+    (covariance_k, gicp_epsilon).  Returns per pair the dict of Context.gicp (without the transformed cloud): T is the total source->target
+    pose, Rt_refined the same as f64."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    HS = (C.c_void_p * n)(*[a.h.value for a, _ in pairs])
+    HT = (C.c_void_p * n)(*[b.h.value for _, b in pairs])
+    init = None
+    if Rt_init is not None:
+        init = np.ascontiguousarray(Rt_init, dtype=np.float64).reshape(n, 16)
+    res = (GicpResult * n)()
+    self._check(self.lib.ghicp_gicp_clouds(self.h, C.byref(params), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
+                                           int(max_concurrent), res))
+    out = []
+    for r in res:
+        d = {k: getattr(r.stats, k) for k, _ in IcpStats._fields_ if k != "pad_"}
+        T = np.array(r.T[:], np.float32).reshape(4, 4)
+        d.update(T=T, Rt_refined=T.astype(np.float64))
+        out.append(d)
+    return out
+
+
 Context.cloud_create = _cloud_create
+Context.gicp_clouds = _gicp_clouds
 Context.refine_clouds = _refine_clouds
 Context.clouds_recompute = _clouds_recompute
 Context.cloud_from_features = _cloud_from_features

@@ -20,7 +20,18 @@ struct ghicp_cloud {
   DevBuf rf_fpts, rf_fstart, rf_cpts, rf_cstart, rf_nrm;
   void rf_invalidate() { rf_ready = false; rf_k = 0; }
   void rf_release() { rf_invalidate(); rf_fpts.release(); rf_fstart.release(); rf_cpts.release(); rf_cstart.release(); rf_nrm.release(); }
+  // what it needs for the batched generalized ICP (ghicp_cloud_prepare_gicp, refine_gicp.hip), as source or target: the m x 6 f64
+  // regularised covariances of ds for (gc_k, gc_eps).  Invalid after every recompute; ghicp_cloud_prepare_refine keeps them.
+  bool gc_ready = false;
+  int gc_k = 0;
+  double gc_eps = 0.0;
+  DevBuf gc_cov;
+  void gc_invalidate() { gc_ready = false; gc_k = 0; gc_eps = 0.0; }
+  void gc_release() { gc_invalidate(); gc_cov.release(); }
 };
+
+// the fine + coarse 1-NN grids over c->ds into the handle's own buffers (refine.hip); the caller sets rf_ready once the stream is idle
+int gh_cloud_build_grids(ghicp_ctx* ctx, ghicp_cloud* c);
 
 inline bool same_front_end(const ghicp_pair_config& a, const ghicp_pair_config& b) {
   return a.reg.feature == b.reg.feature && a.reg.dof == b.reg.dof && a.reg.radius_nonmax == b.reg.radius_nonmax && a.voxel == b.voxel &&

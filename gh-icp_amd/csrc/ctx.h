@@ -83,6 +83,7 @@ enum BufSlot {
   B_SOR_DIST, B_SOR_PART,
   // batched fine registration over cached clouds (refine.hip): pair descriptors, per-pair counters and flags (the concatenated per-point
   // arrays, states, partials and histograms of a chunk reuse the B_ICP_* slots of the single-pair loop)
+  // (the batched generalized ICP, refine_gicp.hip, uses the same two and B_GICP_MAHAL for the chunk's Mahalanobis matrices)
   B_RF_DESC, B_RF_MISC,
   B_NUM
 };
@@ -93,9 +94,10 @@ enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_F
               KT_TRANSFORM,                                                  // S7 of a batch (ghicp_transform_clouds)
               KT_PAIR_LOOP_DISPATCH,                                         // ONE k_pair_loop dispatch (a class launch of a batch), timed on the stream it runs on -- what rocprofv3's kernel trace reports per row
               KT_REFINE,                                                     // one chunk of the batched fine registration (refine.hip): upload -> final states
+              KT_GICP_CLOUDS,                                                // one chunk of the batched generalized ICP (refine_gicp.hip): upload -> final states
               KT_NUM };
 static const char* const kKtNames[KT_NUM] = {"pca_cells", "bsc", "km_solve", "cd_rowmin", "km_weights", "fd_bsc", "nms_round", "voxel_sort",
-                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine"};
+                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds"};
 
 struct ghicp_ctx {
   // optional per-kernel timing

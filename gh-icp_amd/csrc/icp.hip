@@ -206,219 +206,27 @@ int overlap_dev(ghicp_ctx* ctx, const float* d1, long long n1, int s1, const flo
 // CRegistration::gicp_reg (common_reg.cpp:216-284) = pcl::GeneralizedIterativeClosestPoint as recalled in ghicp_c.h, with the inner
 // solver of DESIGN.md N8.  Per outer iteration: k_gicp_apply, the 1-NN search, k_gicp_mahal, k_gicp_prep, max_inner_iter x
 // (k_gicp_acc, k_gicp_solve), k_gicp_outer, one status read.  The inner steps after the stop flag are no-ops.
-struct GicpState {
-  float T[16];                   // transformation_
-  double x[6];                   // (tx, ty, tz, roll, pitch, yaw) of the inner problem
-  double R[9], dR[27];           // R(x) and dR/droll, dR/dpitch, dR/dyaw at x (f64)
-  double maxd2, inv_eps_r, inv_eps_t, mse;
-  unsigned count;                // correspondences of this iteration
-  int iterations, max_iter, converged, reason, inner_done, inner_steps, pad_;
-};
-
-constexpr double kGicpStop = 1e-10;  // N8: the inner loop stops once max |dx| < this
-
-// R(x) = Rz(yaw) Ry(pitch) Rx(roll) and its three partial derivatives, f64
-__device__ inline void gicp_rot(const double* x, double* R, double* dR) {
-  const double ca = cos(x[3]), sa = sin(x[3]), cb = cos(x[4]), sb = sin(x[4]), cg = cos(x[5]), sg = sin(x[5]);
-  const double r[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                       -sb, cb * sa, cb * ca};
-  const double da[9] = {0, cg * sb * ca + sg * sa, -cg * sb * sa + sg * ca,
-                        0, sg * sb * ca - cg * sa, -sg * sb * sa - cg * ca,
-                        0, cb * ca, -cb * sa};
-  const double db[9] = {-cg * sb, cg * cb * sa, cg * cb * ca,
-                        -sg * sb, sg * cb * sa, sg * cb * ca,
-                        -cb, -sb * sa, -sb * ca};
-  const double dg[9] = {-sg * cb, -sg * sb * sa - cg * ca, -sg * sb * ca + cg * sa,
-                        cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                        0, 0, 0};
-  for (int e = 0; e < 9; e++) { R[e] = r[e]; dR[e] = da[e]; dR[9 + e] = db[e]; dR[18 + e] = dg[e]; }
-}
-
-__device__ inline void gicp_state_rot(GicpState* st) {
-  double R[9], dR[27];
-  gicp_rot(st->x, R, dR);
-  for (int e = 0; e < 9; e++) st->R[e] = R[e];
-  for (int e = 0; e < 27; e++) st->dR[e] = dR[e];
-}
-
+// the bodies are in icp_dev.h, shared with the batched loop over cached clouds (refine_gicp.hip)
 __global__ __launch_bounds__(256) void k_gicp_apply(const float4* __restrict__ src, int n, const GicpState* __restrict__ st, float4* __restrict__ cur) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float* M = st->T;
-  const float4 P = src[i];
-  cur[i] = make_float4(((M[0] * P.x + M[1] * P.y) + M[2] * P.z) + M[3], ((M[4] * P.x + M[5] * P.y) + M[6] * P.z) + M[7],
-                       ((M[8] * P.x + M[9] * P.y) + M[10] * P.z) + M[11], 0.f);
+  gicp_apply_body(src, n, blockIdx.x * 256 + threadIdx.x, st, cur);
 }
 
-// M_i = (R C_S,i R^T + C_T,j)^-1 (symmetric: upper triangle of R C R^T + C_T, inverse by cofactors) for every correspondence with
-// d^2 < max distance^2; rejected points get nn = -1.  Block partials: [0] accepted count, [1] sum of their d^2.
 __global__ __launch_bounds__(256) void k_gicp_mahal(int* __restrict__ nn, const float* __restrict__ nd, int ns, const double* __restrict__ covS,
                                                     const double* __restrict__ covT, const GicpState* __restrict__ st, double* __restrict__ mahal,
                                                     double* __restrict__ part) {
-  __shared__ double red[16];
-  double R[9];
-  for (int e = 0; e < 9; e++) R[e] = (double)st->T[(e / 3) * 4 + e % 3];
-  const double maxd2 = st->maxd2;
-  double acc[2] = {0, 0};
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)ns; i += NBLK * 256u) {
-    const int j = nn[i];
-    if (j < 0) continue;
-    if (!((double)nd[i] < maxd2)) { nn[i] = -1; continue; }
-    const double* cs = &covS[(size_t)i * 6];
-    const double* ct = &covT[(size_t)j * 6];
-    const double C[9] = {cs[0], cs[1], cs[2], cs[1], cs[3], cs[4], cs[2], cs[4], cs[5]};
-    double P[9];
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) P[r * 3 + c] = (R[r * 3] * C[c] + R[r * 3 + 1] * C[3 + c]) + R[r * 3 + 2] * C[6 + c];
-    const int rr[6] = {0, 0, 0, 1, 1, 2}, cc[6] = {0, 1, 2, 1, 2, 2};
-    double A[6];
-    for (int e = 0; e < 6; e++) {
-      const int r = rr[e], c = cc[e];
-      A[e] = ((P[r * 3] * R[c * 3] + P[r * 3 + 1] * R[c * 3 + 1]) + P[r * 3 + 2] * R[c * 3 + 2]) + ct[e];
-    }
-    const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5];
-    const double k00 = d * f - e * e, k01 = c * e - b * f, k02 = b * e - c * d, k11 = a * f - c * c, k12 = b * c - a * e, k22 = a * d - b * b;
-    const double det = (a * k00 + b * k01) + c * k02;
-    double* M = &mahal[(size_t)i * 6];
-    M[0] = k00 / det; M[1] = k01 / det; M[2] = k02 / det; M[3] = k11 / det; M[4] = k12 / det; M[5] = k22 / det;
-    acc[0] += 1.0;
-    acc[1] += (double)nd[i];
-  }
-  store_partials(acc, 2, red, part, blockIdx.x);
+  gicp_mahal_body(nn, nd, ns, covS, covT, st, mahal, part, blockIdx.x);
 }
 
-// count and MSE of the correspondences; fewer than 4: PCL throws, the loop ends unconverged.  Else x0 = parameters of transformation_.
-__global__ __launch_bounds__(64) void k_gicp_prep(GicpState* st, const double* __restrict__ part) {
-  const double cnt = wave_reduce_partials(part, 0), d2 = wave_reduce_partials(part, 1);
-  if (threadIdx.x != 0) return;
-  st->count = (unsigned)cnt;
-  st->mse = cnt > 0 ? d2 / cnt : 0.0;
-  st->inner_steps = 0;
-  if (cnt < 4.0) {
-    st->inner_done = 1;
-    st->converged = 0;
-    st->reason = GHICP_ICP_NO_CORRESPONDENCES;
-    return;
-  }
-  st->inner_done = 0;
-  const float* T = st->T;
-  st->x[0] = (double)T[3]; st->x[1] = (double)T[7]; st->x[2] = (double)T[11];
-  st->x[3] = atan2((double)T[9], (double)T[10]);
-  st->x[4] = asin(fmin(1.0, fmax(-1.0, -(double)T[8])));
-  st->x[5] = atan2((double)T[4], (double)T[0]);
-  gicp_state_rot(st);
-}
+__global__ __launch_bounds__(64) void k_gicp_prep(GicpState* st, const double* __restrict__ part) { gicp_prep_body(st, part); }
 
-// one Gauss-Newton step's sums over the correspondences: J^T M J (21, upper triangle row by row), J^T M r (6), r^T M r (1);
-// r = R(x) s + t(x) - t_j and J = [I | dR/droll s, dR/dpitch s, dR/dyaw s], all f64
 __global__ __launch_bounds__(256) void k_gicp_acc(const float4* __restrict__ src, const float4* __restrict__ tgt, const int* __restrict__ nn, int ns,
                                                   const double* __restrict__ mahal, const GicpState* __restrict__ st, double* __restrict__ part) {
-  if (st->inner_done) return;
-  __shared__ double red[16];
-  double R[9], dR[27], x[6];
-  for (int e = 0; e < 9; e++) R[e] = st->R[e];
-  for (int e = 0; e < 27; e++) dR[e] = st->dR[e];
-  for (int e = 0; e < 6; e++) x[e] = st->x[e];
-  double acc[28];
-#pragma unroll
-  for (int d = 0; d < 28; d++) acc[d] = 0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)ns; i += NBLK * 256u) {
-    const int j = nn[i];
-    if (j < 0) continue;
-    const float4 S = src[i], D = tgt[j];
-    const double s[3] = {(double)S.x, (double)S.y, (double)S.z};
-    double r[3], J[3][6];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      r[q] = (((R[q * 3] * s[0] + R[q * 3 + 1] * s[1]) + R[q * 3 + 2] * s[2]) + x[q]) - (q == 0 ? (double)D.x : (q == 1 ? (double)D.y : (double)D.z));
-#pragma unroll
-      for (int p = 0; p < 3; p++) J[q][p] = q == p ? 1.0 : 0.0;
-#pragma unroll
-      for (int a = 0; a < 3; a++) J[q][3 + a] = (dR[a * 9 + q * 3] * s[0] + dR[a * 9 + q * 3 + 1] * s[1]) + dR[a * 9 + q * 3 + 2] * s[2];
-    }
-    const double* m = &mahal[(size_t)i * 6];
-    const double M[9] = {m[0], m[1], m[2], m[1], m[3], m[4], m[2], m[4], m[5]};
-    double Mr[3], MJ[3][6];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      Mr[q] = (M[q * 3] * r[0] + M[q * 3 + 1] * r[1]) + M[q * 3 + 2] * r[2];
-#pragma unroll
-      for (int p = 0; p < 6; p++) MJ[q][p] = (M[q * 3] * J[0][p] + M[q * 3 + 1] * J[1][p]) + M[q * 3 + 2] * J[2][p];
-    }
-    int k = 0;
-#pragma unroll
-    for (int p = 0; p < 6; p++)
-#pragma unroll
-      for (int q = p; q < 6; q++) acc[k++] += (J[0][p] * MJ[0][q] + J[1][p] * MJ[1][q]) + J[2][p] * MJ[2][q];
-#pragma unroll
-    for (int p = 0; p < 6; p++) acc[21 + p] += (J[0][p] * Mr[0] + J[1][p] * Mr[1]) + J[2][p] * Mr[2];
-    acc[27] += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
-  }
-  store_partials(acc, 28, red, part, blockIdx.x);
+  gicp_acc_body(src, tgt, nn, ns, mahal, st, part, blockIdx.x);
 }
 
-// the step: partials reduced in wave_reduce_partials order, each group (H, g, e) rounded by N2, H dx = -g by elimination with partial
-// pivoting, x += dx; a singular or non-finite solve stops the inner loop without a step
-__global__ __launch_bounds__(64) void k_gicp_solve(GicpState* st, const double* __restrict__ part) {
-  if (st->inner_done) return;
-  double acc[28];
-  for (int d = 0; d < 28; d++) acc[d] = wave_reduce_partials(part, d);
-  if (threadIdx.x != 0) return;
-  gh_quant_grid(acc, 21);
-  gh_quant_grid(acc + 21, 6);
-  double A[6][6], bb[6], dx[6];
-  int k = 0;
-  for (int r = 0; r < 6; r++)
-    for (int q = r; q < 6; q++) { A[r][q] = acc[k]; A[q][r] = acc[k]; k++; }
-  for (int r = 0; r < 6; r++) bb[r] = -acc[21 + r];
-  for (int c = 0; c < 6; c++) {
-    int piv = c;
-    for (int r = c + 1; r < 6; r++) if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
-    if (piv != c) {
-      for (int q = 0; q < 6; q++) { const double t = A[c][q]; A[c][q] = A[piv][q]; A[piv][q] = t; }
-      const double t = bb[c]; bb[c] = bb[piv]; bb[piv] = t;
-    }
-    for (int r = c + 1; r < 6; r++) {
-      const double f = A[r][c] / A[c][c];
-      for (int q = c; q < 6; q++) A[r][q] -= f * A[c][q];
-      bb[r] -= f * bb[c];
-    }
-  }
-  double mx = 0;
-  for (int r = 5; r >= 0; r--) {
-    double s = bb[r];
-    for (int q = r + 1; q < 6; q++) s -= A[r][q] * dx[q];
-    dx[r] = s / A[r][r];
-    mx = fmax(mx, fabs(dx[r]));
-  }
-  st->inner_steps++;
-  if (!(mx <= 1e300)) { st->inner_done = 1; return; }  // singular / non-finite: no step
-  for (int p = 0; p < 6; p++) st->x[p] += dx[p];
-  gicp_state_rot(st);
-  if (mx < kGicpStop) st->inner_done = 1;
-}
+__global__ __launch_bounds__(64) void k_gicp_solve(GicpState* st, const double* __restrict__ part) { gicp_solve_body(st, part); }
 
-// applyState in float (the f64 closed form of R(x) rounded entry by entry), then the delta test of GICP's computeTransformation
-__global__ void k_gicp_outer(GicpState* st) {
-  if (st->reason == GHICP_ICP_NO_CORRESPONDENCES) return;
-  float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) T[r * 4 + c] = (float)st->R[r * 3 + c];
-    T[r * 4 + 3] = (float)st->x[r];
-  }
-  double delta = 0;
-  for (int r = 0; r < 4; r++)
-    for (int c = 0; c < 4; c++) {
-      const double ratio = (r < 3 && c < 3) ? st->inv_eps_r : st->inv_eps_t;
-      const double cd = ratio * fabs((double)st->T[r * 4 + c] - (double)T[r * 4 + c]);
-      if (cd > delta) delta = cd;
-    }
-  for (int d = 0; d < 16; d++) st->T[d] = T[d];
-  st->iterations++;
-  if (st->iterations >= st->max_iter) { st->converged = 1; st->reason = GHICP_ICP_ITERATIONS; }
-  else if (delta < 1.0) { st->converged = 1; st->reason = GHICP_ICP_TRANSFORM; }
-}
+__global__ void k_gicp_outer(GicpState* st) { gicp_outer_body(st); }
 
 }  // namespace
 
@@ -672,11 +480,24 @@ extern "C" int ghicp_gicp_covariances(ghicp_ctx* ctx, const float* xyz, int64_t 
 
 extern "C" int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
                           const ghicp_gicp_params* P, float* T16, float* transformed, ghicp_icp_stats* stats) {
+  return ghicp_gicp_from(ctx, xyzS, ns, strideS, xyzT, nt, strideT, P, nullptr, T16, transformed, stats);
+}
+
+// gicp_reg with transformation_ starting at guess16 (NULL: the identity, which is ghicp_gicp).  The source points and their covariances stay
+// in the source's own frame: k_gicp_apply moves the points by transformation_, k_gicp_mahal rotates C_S by its R, k_gicp_prep takes x from it.
+extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                               const ghicp_gicp_params* P, const float* guess16, float* T16, float* transformed, ghicp_icp_stats* stats) {
   GH_ENTER(ctx);
   GH_ARG(P != nullptr && T16 != nullptr && stats != nullptr && ns >= 0 && nt >= 0 && ns < (1ll << 31) - 2 && nt < (1ll << 31) - 2 && strideS >= 3 &&
          strideT >= 3);
   GH_ARG(P->covariance_k >= 1 && P->covariance_k <= 20 && P->max_inner_iter >= 1 && P->max_inner_iter <= 100);
   GH_ARG(P->max_correspondence_distance > 0.0 && P->gicp_epsilon > 0.0 && P->transformation_epsilon > 0.0 && P->rotation_epsilon > 0.0);
+  if (P->use_trimmed) GH_ARG(P->thre_dis > 0.f);
+  const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float T0[16];
+  memcpy(T0, guess16 ? guess16 : I16, sizeof(T0));
+  for (int e = 0; e < 16; e++) GH_ARG(std::isfinite(T0[e]));
+  GH_ARG(T0[12] == 0.f && T0[13] == 0.f && T0[14] == 0.f && T0[15] == 1.f);
   hipStream_t s = ctx->stream;
   memset(stats, 0, sizeof(*stats));
   Stager sg(ctx);
@@ -687,20 +508,27 @@ extern "C" int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int str
   GH_TRY(sg.out(transformed, (size_t)ns * 3, &dOut));
 
   if (P->use_trimmed) {  // common_reg.cpp:240-246: the only effect of the trimmed flag on GICP (the rejector is never consulted)
-    GH_ARG(P->thre_dis > 0.f);
     float ratio = 0.f;
-    GH_TRY(overlap_dev(ctx, dS, ns, strideS, dT, nt, strideT, P->thre_dis, &ratio));
+    if (guess16 && ns > 0) {  // the gate sees the source where the guess puts it (the float expression of k_gicp_apply)
+      float4* moved;
+      GH_TRY(ctx->reserve(B_ICP_CUR, (size_t)ns + 1, &moved));
+      M16 M;
+      memcpy(M.m, T0, sizeof(M.m));
+      hipLaunchKernelGGL(k_transform_f32, dim3(cdiv(ns, 256)), dim3(256), 0, s, dS, (long long)ns, strideS, M, (float*)nullptr, moved);
+      GH_TRY(overlap_dev(ctx, reinterpret_cast<const float*>(moved), ns, 4, dT, nt, strideT, P->thre_dis, &ratio));
+    } else {
+      GH_TRY(overlap_dev(ctx, dS, ns, strideS, dT, nt, strideT, P->thre_dis, &ratio));
+    }
     stats->overlap = ratio;
     if (ratio < P->min_overlap) { sg.outs.clear(); return GHICP_OK; }  // "This registration would not be done"
   }
   stats->done = 1;
-  const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (ns == 0 || nt == 0) {
     stats->reason = GHICP_ICP_NO_CORRESPONDENCES;
-    memcpy(T16, I16, sizeof(I16));
+    memcpy(T16, T0, sizeof(T0));
     if (ns > 0 && dOut) {
       M16 M;
-      memcpy(M.m, I16, sizeof(I16));
+      memcpy(M.m, T0, sizeof(T0));
       hipLaunchKernelGGL(k_transform_f32, dim3(cdiv(ns, 256)), dim3(256), 0, s, dS, (long long)ns, strideS, M, dOut, (float4*)nullptr);
     }
     return sg.finish();
@@ -733,7 +561,7 @@ extern "C" int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int str
 
   GicpState hst;
   memset(&hst, 0, sizeof(hst));
-  memcpy(hst.T, I16, sizeof(I16));
+  memcpy(hst.T, T0, sizeof(T0));
   hst.maxd2 = P->max_correspondence_distance * P->max_correspondence_distance;
   hst.inv_eps_r = 1.0 / P->rotation_epsilon;
   hst.inv_eps_t = 1.0 / P->transformation_epsilon;

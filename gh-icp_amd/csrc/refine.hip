@@ -206,6 +206,27 @@ void mat4_to_result(const float* T_icp, const float* init_f, ghicp_refine_result
 
 }  // namespace
 
+int gh_cloud_build_grids(ghicp_ctx* ctx, ghicp_cloud* c) {
+  hipStream_t s = ctx->stream;
+  memset(&c->rf_fine, 0, sizeof(GridDesc));
+  memset(&c->rf_coarse, 0, sizeof(GridDesc));
+  if (c->m <= 0) return GHICP_OK;
+  icpdev::NnIndex X;
+  GH_TRY(gh_icp_build_index(ctx, reinterpret_cast<const float*>(c->ds.p), c->m, 4, &X));
+  // out of the context's grid buffers into the handle's own
+  GH_HIP(c->rf_fpts.reserve((size_t)c->m * sizeof(float4)));
+  GH_HIP(c->rf_cpts.reserve((size_t)c->m * sizeof(float4)));
+  GH_HIP(c->rf_fstart.reserve(((size_t)X.fine.d.ncell + 1) * sizeof(unsigned)));
+  GH_HIP(c->rf_cstart.reserve(((size_t)X.coarse.d.ncell + 1) * sizeof(unsigned)));
+  GH_HIP(hipMemcpyAsync(c->rf_fpts.p, X.fine.pts, (size_t)c->m * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  GH_HIP(hipMemcpyAsync(c->rf_cpts.p, X.coarse.pts, (size_t)c->m * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  GH_HIP(hipMemcpyAsync(c->rf_fstart.p, X.fine.start, ((size_t)X.fine.d.ncell + 1) * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+  GH_HIP(hipMemcpyAsync(c->rf_cstart.p, X.coarse.start, ((size_t)X.coarse.d.ncell + 1) * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+  c->rf_fine = X.fine.d;
+  c->rf_coarse = X.coarse.d;
+  return GHICP_OK;
+}
+
 extern "C" int ghicp_cloud_prepare_refine(ghicp_cloud* c, int32_t covariance_k) {
   if (!c || !c->ctx) return GHICP_ERR_ARG;
   ghicp_ctx* ctx = c->ctx;
@@ -217,25 +238,7 @@ extern "C" int ghicp_cloud_prepare_refine(ghicp_cloud* c, int32_t covariance_k) 
   const bool had_grids = c->rf_ready;
   const int had_k = c->rf_k;
   c->rf_invalidate();  // until everything below is in place
-  if (!had_grids) {
-    memset(&c->rf_fine, 0, sizeof(GridDesc));
-    memset(&c->rf_coarse, 0, sizeof(GridDesc));
-    if (c->m > 0) {
-      icpdev::NnIndex X;
-      GH_TRY(gh_icp_build_index(ctx, ds, c->m, 4, &X));
-      // out of the context's grid buffers into the handle's own
-      GH_HIP(c->rf_fpts.reserve((size_t)c->m * sizeof(float4)));
-      GH_HIP(c->rf_cpts.reserve((size_t)c->m * sizeof(float4)));
-      GH_HIP(c->rf_fstart.reserve(((size_t)X.fine.d.ncell + 1) * sizeof(unsigned)));
-      GH_HIP(c->rf_cstart.reserve(((size_t)X.coarse.d.ncell + 1) * sizeof(unsigned)));
-      GH_HIP(hipMemcpyAsync(c->rf_fpts.p, X.fine.pts, (size_t)c->m * sizeof(float4), hipMemcpyDeviceToDevice, s));
-      GH_HIP(hipMemcpyAsync(c->rf_cpts.p, X.coarse.pts, (size_t)c->m * sizeof(float4), hipMemcpyDeviceToDevice, s));
-      GH_HIP(hipMemcpyAsync(c->rf_fstart.p, X.fine.start, ((size_t)X.fine.d.ncell + 1) * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
-      GH_HIP(hipMemcpyAsync(c->rf_cstart.p, X.coarse.start, ((size_t)X.coarse.d.ncell + 1) * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
-      c->rf_fine = X.fine.d;
-      c->rf_coarse = X.coarse.d;
-    }
-  }
+  if (!had_grids) GH_TRY(gh_cloud_build_grids(ctx, c));
   if (covariance_k > 0 && (covariance_k != had_k || !had_grids)) {
     GH_HIP(c->rf_nrm.reserve(((size_t)c->m * 3 + 3) * sizeof(float)));
     GH_TRY(gh_knn_normals_dev(ctx, ds, c->m, 4, covariance_k, c->rf_nrm.as<float>()));

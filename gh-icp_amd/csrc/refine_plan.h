@@ -1,4 +1,4 @@
-// Internal: how ghicp_refine_clouds cuts its pairs into chunks (pairs that share one launch sequence).  Plain C++, no HIP: the planner is
+// Internal: how ghicp_refine_clouds and ghicp_gicp_clouds cut their pairs into chunks (pairs that share one launch sequence).  Plain C++, no HIP: the planner is
 // compiled on its own by tests/cpp/test_refine_plan.cpp.
 #pragma once
 #include <cstddef>
@@ -14,14 +14,16 @@ constexpr size_t kRefinePointBytes = 16 + 4 + 4 + 4;     // cur, nn, nd, work li
 // Chunk boundaries b[0] = 0 < b[1] < ... < b.back() = n_pairs over the pairs in the given order (empty list: {0}).  max_concurrent > 0: chunks of
 // exactly that many pairs (the last one shorter), capped at kRefineMaxChunk.  0: as many pairs per chunk as fit `budget` bytes by the per-pair
 // and per-point costs above, at least one.  ns[p]: source points of pair p.
-inline std::vector<int> gh_refine_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget) {
+// pair_bytes / point_bytes: the costs of the loop that is planned (defaults: ghicp_refine_clouds).
+inline std::vector<int> gh_refine_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget, size_t pair_bytes = kRefinePairBytes,
+                                       size_t point_bytes = kRefinePointBytes) {
   std::vector<int> b(1, 0);
   if (n_pairs <= 0) return b;
   const int cap = max_concurrent > 0 && max_concurrent < kRefineMaxChunk ? max_concurrent : kRefineMaxChunk;
   size_t used = 0;
   int in_chunk = 0;
   for (int p = 0; p < n_pairs; p++) {
-    const size_t cost = kRefinePairBytes + kRefinePointBytes * (size_t)(ns[p] > 0 ? ns[p] : 0);
+    const size_t cost = pair_bytes + point_bytes * (size_t)(ns[p] > 0 ? ns[p] : 0);
     const bool full = in_chunk >= cap || (max_concurrent <= 0 && in_chunk > 0 && used + cost > budget);
     if (full) { b.push_back(p); used = 0; in_chunk = 0; }
     used += cost;
@@ -29,4 +31,12 @@ inline std::vector<int> gh_refine_plan(int n_pairs, const int64_t* ns, int max_c
   }
   b.push_back(n_pairs);
   return b;
+}
+
+// ghicp_gicp_clouds (refine_gicp.hip): per point the 48 B Mahalanobis matrix on top of cur / nn / nd / work list; per pair the partial records
+// and a state record, no select histograms.
+constexpr size_t kGicpPairBytes = 512 * 32 * 8 + 1024;
+constexpr size_t kGicpPointBytes = kRefinePointBytes + 48;
+inline std::vector<int> gh_gicp_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget) {
+  return gh_refine_plan(n_pairs, ns, max_concurrent, budget, kGicpPairBytes, kGicpPointBytes);
 }

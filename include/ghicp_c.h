@@ -403,6 +403,21 @@ int ghicp_gicp_params_default(ghicp_gicp_params* p);
 int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
                const ghicp_gicp_params* params, float* T16 /*[host]*/, float* transformed, ghicp_icp_stats* stats /*[host]*/);
 
+/* ghicp_gicp from an initial pose: transformation_ starts at guess16 (row-major float 4x4 [host], source -> target; NULL: the identity,
+ * which is ghicp_gicp itself, bit for bit).  The source points and the source covariances stay in the source's OWN frame: every outer
+ * iteration moves the points by the current transformation_ for the 1-NN search and rotates C_S,i by its R (M_i above), so covariances
+ * computed once per cloud serve every pair and every guess.  As recalled (same caveat as above), this is what PCL's own
+ * align(output, guess) does.  The reference calls align without a guess (common_reg.cpp:216-284): the guess is an EXTENSION of this ABI,
+ * the stage after a coarse GH-ICP pose.
+ *   overlap gate  with use_trimmed: calOverlap of the guess-moved source (the float expression of ghicp_transform_cloud_f32) against T
+ *   outputs       T16 = the final transformation_, the TOTAL source -> target pose (guess included); transformed = T16 * S.  Fewer than 4
+ *                 correspondences: T16 = the guess.  A refused pair leaves T16 untouched.
+ *   GHICP_ERR_ARG for a guess with a non-finite entry or a last row other than (0, 0, 0, 1); whether the 3x3 block is a rotation is the
+ *                 caller's business, as everywhere in this ABI. */
+int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                    const ghicp_gicp_params* params, const float* guess16 /*[host] row-major 4x4, NULL = identity*/,
+                    float* T16 /*[host]*/, float* transformed, ghicp_icp_stats* stats /*[host]*/);
+
 /* The regularised covariances of one cloud as ghicp_gicp computes them: n x 6 f64 (c00, c01, c02, c11, c12, c22). k in 1..20. */
 int ghicp_gicp_covariances(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, int k, double eps, double* cov6);
 
@@ -472,6 +487,33 @@ typedef struct ghicp_refine_result {
  * device memory.  Results do not depend on it.  out: n_pairs [host]. */
 int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
                         const double* Rt_init /*[host]*/, int32_t max_concurrent, ghicp_refine_result* out /*[host]*/);
+
+/* ------------------------------------------------------------------------------------------------
+ * Generalized ICP over cached clouds: the loop of ghicp_gicp_from for many pairs of handles at once.  (The reference runs gicp_reg pair
+ * by pair and without a guess; it has no counterpart.)
+ * ------------------------------------------------------------------------------------------------ */
+/* Keeps in the handle what `cloud` needs to serve as SOURCE or TARGET of ghicp_gicp_clouds: the m x 6 f64 regularised covariances of its
+ * down-sampled points for (covariance_k in 1..20, gicp_epsilon > 0), as ghicp_gicp_covariances gives them (48 B per point), and the 1-NN
+ * grids of ghicp_cloud_prepare_refine if the handle does not hold them yet (the same state, built once whichever call comes first).
+ * Calling it again with the same values changes nothing; other values replace the covariances and keep grids and normals.
+ * ghicp_cloud_prepare_refine keeps the covariances.  ghicp_cloud_recompute / ghicp_clouds_recompute invalidate them, ghicp_cloud_destroy
+ * frees them.  The handle is synchronised on return and may then serve any context of the device.  GHICP_ERR_ARG for a handle rebuilt by
+ * ghicp_cloud_from_features (it holds no points). */
+int ghicp_cloud_prepare_gicp(ghicp_cloud* cloud, int32_t covariance_k, double gicp_epsilon);
+
+typedef struct ghicp_gicp_result {
+  float T[16];            /* the final transformation_ (row-major): the total source->target pose; float(Rt_init) for a refused pair */
+  ghicp_icp_stats stats;  /* as ghicp_gicp_from fills it; done = 0: refused by the overlap gate */
+} ghicp_gicp_result;
+
+/* S[p] -> T[p] for n_pairs pairs, from Rt_init (n_pairs x 16 row-major f64 [host]; NULL: identity for every pair).  Pair p comes out as
+ * ghicp_gicp_from(down-sampled S[p], down-sampled T[p], params, float(Rt_init[p])) gives it, bit for bit (T and every field of stats),
+ * whatever the other pairs do and whatever max_concurrent is.  A refused pair gets done = 0, T = float(Rt_init[p]) and overlap filled.
+ * GHICP_ERR_ARG when a handle of a pair does not hold covariances for (params->covariance_k, params->gicp_epsilon), when a target holds no
+ * grids, for a handle without points and for handles of another device; every pair is checked before anything is written or launched.
+ * The handles are const.  max_concurrent as in ghicp_refine_clouds.  out: n_pairs [host]. */
+int ghicp_gicp_clouds(ghicp_ctx* ctx, const ghicp_gicp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                      const double* Rt_init /*[host] n_pairs x 16, NULL = identity*/, int32_t max_concurrent, ghicp_gicp_result* out /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------------
  * Pair queue: independent scan pairs sharded over the GPUs of ONE node, one process per GPU (BASELINE configs[3]).
