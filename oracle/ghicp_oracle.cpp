@@ -167,9 +167,14 @@ static void kabsch_rotation(const double A[3][3], double R[3][3]) {
 // ------------------------------------------------------------------ exact radius search
 // Restates pcl::KdTreeFLANN::radiusSearch semantics: exact, strict d^2 < r^2,
 // float L2 ((dx*dx + dy*dy) + dz*dz), query point included, results sorted by (d^2, index).
-// A uniform hash grid stands in for the KD-tree (same result set, same order).
+// A uniform hash grid stands in for the KD-tree (same result set, same order).  The cell coordinates are taken in double: v - mn is then
+// exact and the product is off by 1e-16 of the coordinate, so the callers' margin of 1e-4 cells holds at any extent (in float the
+// rounding of v - mn moves a cell boundary by half a float step of the extent, and from a few thousand cells per axis on two points
+// closer than the radius could land two cells apart: neighbours were lost).  Above 2^26 cells the cell is coarsened (a larger cell is a
+// superset search: same result set, and the results are sorted), so that a sparse cloud of large extent needs no table of gigabytes.
 struct Grid {
-  float cell, inv;
+  float cell;  // <= the cell in use (knn_grid's bound on the distance of unscanned shells)
+  double inv;
   float mn[3];
   int dim[3];
   std::vector<int> start, order;
@@ -177,7 +182,8 @@ struct Grid {
   int n = 0;
   int stride = 3;
   void build(const float* p, int n_, int stride_, float cell_) {
-    xyz = p; n = n_; stride = stride_; cell = cell_; inv = 1.0f / cell_;
+    xyz = p; n = n_; stride = stride_;
+    double cell_d = (double)cell_;
     float mx[3] = {-3e38f, -3e38f, -3e38f};
     mn[0] = mn[1] = mn[2] = 3e38f;
     for (int i = 0; i < n; i++)
@@ -186,8 +192,16 @@ struct Grid {
         mx[d] = std::max(mx[d], p[(size_t)i * stride + d]);
       }
     if (n == 0) mn[0] = mn[1] = mn[2] = mx[0] = mx[1] = mx[2] = 0;
-    for (int d = 0; d < 3; d++) dim[d] = (int)std::floor((mx[d] - mn[d]) * inv) + 1;
-    size_t nc = (size_t)dim[0] * dim[1] * dim[2];
+    size_t nc;
+    for (;;) {
+      inv = 1.0 / cell_d;
+      for (int d = 0; d < 3; d++) dim[d] = (int)std::floor(((double)mx[d] - (double)mn[d]) * inv) + 1;
+      nc = (size_t)dim[0] * dim[1] * dim[2];
+      if (nc <= ((size_t)1 << 26)) break;
+      cell_d *= 1.5;
+    }
+    cell = (float)cell_d;
+    if ((double)cell > cell_d) cell = std::nextafter(cell, 0.0f);
     start.assign(nc + 1, 0);
     std::vector<int> cellof(n);
     for (int i = 0; i < n; i++) {
@@ -201,7 +215,7 @@ struct Grid {
     for (int i = 0; i < n; i++) order[cur[cellof[i]]++] = i;
   }
   inline int coord(float v, int d) const {
-    int c = (int)std::floor((v - mn[d]) * inv);
+    int c = (int)std::floor(((double)v - (double)mn[d]) * inv);
     return std::min(std::max(c, 0), dim[d] - 1);
   }
   inline int cell_index(const float* q) const { return (coord(q[0], 0) * dim[1] + coord(q[1], 1)) * dim[2] + coord(q[2], 2); }

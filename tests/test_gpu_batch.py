@@ -76,8 +76,7 @@ def test_batch_matches_oracle_keypoints(ctx, api, synth, oracle):
         f, _, _ = oracle.bsc(ds, kp, cfg.reg.radius_nonmax, 6, synth.bsc_pattern_glibc())
         got = d["feat"].cpu().numpy()
         assert got.shape == f.shape
-        bad = np.flatnonzero((got != f).any(axis=(0, 2)))
-        assert bad.size <= max(1, kp.size // 100), bad.size  # N2/N4 of the numerics contract: a bit on < 1 % of the keypoints
+        np.testing.assert_array_equal(got, f)  # N4 of the numerics contract: the strings are exact (contract expf, integer depth sums)
 
 
 def test_batch_edge_cases(ctx, api, synth):
