@@ -55,7 +55,8 @@ EXPORTS = [
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
     "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
-    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds", "ghicp_sbf_write", "ghicp_sbf_read",
+    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds",
+    "ghicp_cloud_prepare_overlap", "ghicp_overlap_clouds", "ghicp_overlap_matrix", "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
     "ghicp_pairqueue_barrier", "ghicp_pairqueue_static_share", "ghicp_pairqueue_claim", "ghicp_pairqueue_counter_reset",
     "ghicp_pairqueue_gather_records", "ghicp_pairqueue_pack_records", "ghicp_pairqueue_register_pairs",
@@ -123,6 +124,11 @@ class RefineResult(C.Structure):
 class GicpResult(C.Structure):
     """ghicp_gicp_result: one pair of ghicp_gicp_clouds."""
     _fields_ = [("T", C.c_float * 16), ("stats", IcpStats)]
+
+
+class OverlapResult(C.Structure):
+    """ghicp_overlap_result: one pair of ghicp_overlap_clouds."""
+    _fields_ = [("hits", C.c_int64), ("n", C.c_int64), ("ratio", C.c_float), ("pad_", C.c_int32)]
 
 
 def icp_params(max_iter=50, reciprocal=False, trimmed=False, metric=ICP_POINT_TO_POINT, thre_dis=0.5, min_overlap=0.1,
@@ -764,6 +770,12 @@ class Cloud:
         self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_gicp(self.h, int(k), C.c_double(eps)))
         return self
 
+    def prepare_overlap(self, thre_dis):
+        """What the cloud needs to serve as a target of Context.overlap_clouds / overlap_matrix: its search grid of cell thre_dis.
+        Needed again after every recompute."""
+        self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_overlap(self.h, C.c_float(thre_dis)))
+        return self
+
     def close(self):
         if self.h:
             self.ctx.lib.ghicp_cloud_destroy(self.h)
@@ -869,7 +881,41 @@ def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
     return out
 
 
+def _overlap_clouds(self, S, T, thre_dis, Rt=None, max_concurrent=0):
+    """ghicp_overlap_clouds: calOverlap of the down-sampled clouds of S[p] in T[p] (lists of Cloud) under Rt (n x 4 x 4 f64 source->target;
+    None: identity), many pairs per launch.  Targets must have been through Cloud.prepare_overlap(thre_dis).  Returns a dict of numpy arrays:
+    hits (n,) int64, n (n,) int64, ratio (n,) float32."""
+    n = len(S)
+    assert len(T) == n
+    HS = (C.c_void_p * max(n, 1))(*[a.h.value for a in S])
+    HT = (C.c_void_p * max(n, 1))(*[b.h.value for b in T])
+    init = None
+    if Rt is not None:
+        init = np.ascontiguousarray(Rt, dtype=np.float64).reshape(n, 16)
+    res = (OverlapResult * max(n, 1))()
+    self._check(self.lib.ghicp_overlap_clouds(self.h, C.c_float(thre_dis), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
+                                              int(max_concurrent), res))
+    r = np.frombuffer(res, dtype=np.dtype(OverlapResult))[:n]
+    return dict(hits=r["hits"].copy(), n=r["n"].copy(), ratio=r["ratio"].copy())
+
+
+def _overlap_matrix(self, clouds, thre_dis, poses=None):
+    """ghicp_overlap_matrix: the overlap ratio of every cloud i in every cloud j under the cloud->world poses (n x 4 x 4 f64; None: all identity)
+    as an (n, n) float32 array; the diagonal is 1.  Every cloud must have been through Cloud.prepare_overlap(thre_dis)."""
+    n = len(clouds)
+    H = (C.c_void_p * max(n, 1))(*[c.h.value for c in clouds])
+    P = None
+    if poses is not None:
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(n, 16)
+    out = np.zeros((n, n), np.float32)
+    self._check(self.lib.ghicp_overlap_matrix(self.h, C.c_float(thre_dis), n, H, P.ctypes.data_as(C.c_void_p) if P is not None else None,
+                                              out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 Context.cloud_create = _cloud_create
+Context.overlap_clouds = _overlap_clouds
+Context.overlap_matrix = _overlap_matrix
 Context.gicp_clouds = _gicp_clouds
 Context.refine_clouds = _refine_clouds
 Context.clouds_recompute = _clouds_recompute

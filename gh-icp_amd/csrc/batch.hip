@@ -341,6 +341,7 @@ int FbRun::begin(const float* const* xyz, const int64_t* n, int stride) {
     c->n = n[b]; c->m = 0; c->k = 0; c->cand = 0; c->bbx = 0.f;
     c->rf_invalidate();
     c->gc_invalidate();
+    c->ov_invalidate();
     c->V = cfg.reg.dof > 4 ? 4 : (cfg.reg.dof > 0 ? 2 : 1);
     H->c[b].xyz = xyz[b]; H->c[b].n = (int)n[b]; H->c[b].stride = stride;
     H->roff[b + 1] = H->roff[b] + (int)n[b];

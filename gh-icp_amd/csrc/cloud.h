@@ -28,6 +28,15 @@ struct ghicp_cloud {
   DevBuf gc_cov;
   void gc_invalidate() { gc_ready = false; gc_k = 0; gc_eps = 0.0; }
   void gc_release() { gc_invalidate(); gc_cov.release(); }
+  // what it needs to serve as the TARGET of the batched calOverlap (ghicp_cloud_prepare_overlap, overlap_clouds.hip): the search grid of
+  // cell ov_thre over ds -- the grid ghicp_cal_overlap builds over its second cloud on every call.  Invalid after every recompute;
+  // ghicp_cloud_prepare_refine and ghicp_cloud_prepare_gicp keep it.
+  bool ov_ready = false;
+  float ov_thre = 0.f;
+  GridDesc ov_grid;
+  DevBuf ov_pts, ov_start;  // m float4 in cell order; ncell + 1 cell starts
+  void ov_invalidate() { ov_ready = false; ov_thre = 0.f; }
+  void ov_release() { ov_invalidate(); ov_pts.release(); ov_start.release(); }
 };
 
 // the fine + coarse 1-NN grids over c->ds into the handle's own buffers (refine.hip); the caller sets rf_ready once the stream is idle

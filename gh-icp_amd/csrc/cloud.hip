@@ -39,6 +39,7 @@ static int cloud_fill(ghicp_ctx* ctx, ghicp_cloud* c, const float* d, long long 
   c->n = n; c->m = 0; c->k = 0; c->cand = 0;
   c->rf_invalidate();
   c->gc_invalidate();
+  c->ov_invalidate();
   c->V = cfg->reg.dof > 4 ? 4 : (cfg->reg.dof > 0 ? 2 : 1);
   // down-sampling (main:89-90)
   if (cfg->voxel > 0.f) {
@@ -146,6 +147,7 @@ extern "C" int ghicp_cloud_destroy(ghicp_cloud* c) {
   c->ds.release(); c->kp.release(); c->kpx.release(); c->feat.release();
   c->rf_release();
   c->gc_release();
+  c->ov_release();
   delete c;
   return GHICP_OK;
 }

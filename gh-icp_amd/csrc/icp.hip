@@ -57,23 +57,7 @@ __global__ __launch_bounds__(256) void k_overlap(NnGrid G, const float* __restri
   bool hit = false;
   if (i < n) {
     const float px = xyz[i * stride], py = xyz[i * stride + 1], pz = xyz[i * stride + 2];
-    // a query outside the padded grid has no neighbour; inside, the 27 cells around it hold every candidate
-    const float fx = (px - G.d.mn[0]) * G.d.inv, fy = (py - G.d.mn[1]) * G.d.inv, fz = (pz - G.d.mn[2]) * G.d.inv;
-    if (fx >= -1.f && fy >= -1.f && fz >= -1.f && fx <= (float)G.d.dim[0] + 1.f && fy <= (float)G.d.dim[1] + 1.f && fz <= (float)G.d.dim[2] + 1.f) {
-      const int cx = gh_cell_coord(px, G.d.mn[0], G.d.inv, G.d.dim[0]);
-      const int cy = gh_cell_coord(py, G.d.mn[1], G.d.inv, G.d.dim[1]);
-      const int cz = gh_cell_coord(pz, G.d.mn[2], G.d.inv, G.d.dim[2]);
-      gh_for_runs(G.d, G.start, cx, cy, cz, [&](unsigned b, unsigned e) {
-        for (unsigned t = b; t < e && !hit; t++) {
-          const float4 Q = G.pts[t];
-          const float dx = px - Q.x, dy = py - Q.y, dz = pz - Q.z;
-          float d2 = dx * dx;
-          d2 += dy * dy;
-          d2 += dz * dz;
-          if (d2 < r2) hit = true;
-        }
-      });
-    }
+    hit = overlap_hit(G, px, py, pz, r2);  // icp_dev.h
   }
   block_count_add(hit, count);
 }

@@ -242,6 +242,30 @@ __device__ inline void block_count_add(bool flag, unsigned* dst) {
   }
 }
 
+// calOverlap of one query (common_reg.cpp:294-317): does the target hold a point at d^2 < r2?  G has a cell >= the radius: a query outside
+// the padded grid has no neighbour; inside, the 27 cells around it hold every candidate.  Shared by k_overlap (icp.hip) and the batched
+// k_ov_pairs (overlap_clouds.hip).
+__device__ inline bool overlap_hit(const NnGrid& G, float px, float py, float pz, float r2) {
+  bool hit = false;
+  const float fx = (px - G.d.mn[0]) * G.d.inv, fy = (py - G.d.mn[1]) * G.d.inv, fz = (pz - G.d.mn[2]) * G.d.inv;
+  if (fx >= -1.f && fy >= -1.f && fz >= -1.f && fx <= (float)G.d.dim[0] + 1.f && fy <= (float)G.d.dim[1] + 1.f && fz <= (float)G.d.dim[2] + 1.f) {
+    const int cx = gh_cell_coord(px, G.d.mn[0], G.d.inv, G.d.dim[0]);
+    const int cy = gh_cell_coord(py, G.d.mn[1], G.d.inv, G.d.dim[1]);
+    const int cz = gh_cell_coord(pz, G.d.mn[2], G.d.inv, G.d.dim[2]);
+    gh_for_runs(G.d, G.start, cx, cy, cz, [&](unsigned b, unsigned e) {
+      for (unsigned t = b; t < e && !hit; t++) {
+        const float4 Q = G.pts[t];
+        const float dx = px - Q.x, dy = py - Q.y, dz = pz - Q.z;
+        float d2 = dx * dx;
+        d2 += dy * dy;
+        d2 += dz * dz;
+        if (d2 < r2) hit = true;
+      }
+    });
+  }
+  return hit;
+}
+
 // CorrespondenceRejectorTrimmed::getRemainingCorrespondences: floor(overlap_ratio * float(size))
 __device__ inline void icp_prep_body(IcpState* st) {
   unsigned nv = st->count;

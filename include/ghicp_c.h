@@ -516,6 +516,51 @@ int ghicp_gicp_clouds(ghicp_ctx* ctx, const ghicp_gicp_params* params, int32_t n
                       const double* Rt_init /*[host] n_pairs x 16, NULL = identity*/, int32_t max_concurrent, ghicp_gicp_result* out /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------------
+ * calOverlap over cached clouds: which of MANY pairs of handles overlap at all under given poses -- CRegistration::calOverlap
+ * (src/common_reg.cpp:294-317) for every pair of a list in one launch per chunk, before registration (poses from odometry or GNSS), between
+ * coarse and fine registration (drop the pairs whose GH-ICP pose is wrong) or afterwards (edge weights of the scan graph).  (The reference
+ * runs calOverlap pair by pair inside icp_reg / gicp_reg; it has no counterpart.)
+ * ------------------------------------------------------------------------------------------------ */
+/* Keeps in the handle the search grid of cell thre_dis over its down-sampled points (what ghicp_cal_overlap builds for its
+ * second cloud on every call).  Same thre_dis again: nothing happens; another thre_dis replaces the grid.
+ * ghicp_cloud_prepare_refine / ghicp_cloud_prepare_gicp keep it and it leaves their state alone; ghicp_cloud_recompute / ghicp_clouds_recompute
+ * invalidate it, ghicp_cloud_destroy frees it.  The handle is synchronised on return and may then serve any context of the device.
+ * GHICP_ERR_ARG for thre_dis <= 0 and for a handle rebuilt by ghicp_cloud_from_features (it holds no points). */
+int ghicp_cloud_prepare_overlap(ghicp_cloud* cloud, float thre_dis);
+
+typedef struct ghicp_overlap_result {
+  int64_t hits;     /* source points with a target point at d^2 < thre_dis^2 */
+  int64_t n;        /* down-sampled points of the source */
+  float ratio;      /* (float)((0.01 + hits) / (double)n), common_reg.cpp:313; 0 when n == 0 */
+  int32_t pad_;
+} ghicp_overlap_result;
+
+/* S[p] in T[p] for n_pairs pairs under Rt (source->target).  hits and ratio of pair p equal, bit for bit, what
+ * ghicp_transform_cloud_f32(down-sampled S[p], float(Rt[p])) followed by ghicp_cal_overlap(that, down-sampled T[p], thre_dis) gives --
+ * whatever the other pairs are, whatever their order, whatever max_concurrent is.  Empty source: hits = 0, ratio = 0; empty target:
+ * hits = 0, ratio = 0.01 / n (neither launches anything).  The moved source is not stored.
+ * GHICP_ERR_ARG: a target that is not prepared, or prepared for another thre_dis (the floats are compared exactly); a source or target
+ * rebuilt by ghicp_cloud_from_features; a handle of another device; thre_dis <= 0.  Every pair is checked before anything is written or
+ * launched: `out` is untouched then.  Sources need no preparation.  The handles are const: nothing is built lazily, so a prepared handle
+ * may serve any context of the device.
+ * max_concurrent: pairs per launch (chunks of that size, in the given order; at most 4096); 0: chosen by the library. */
+int ghicp_overlap_clouds(ghicp_ctx* ctx, float thre_dis, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                         const double* Rt /*[host] n_pairs x 16 row-major source->target, NULL = identity*/,
+                         int32_t max_concurrent, ghicp_overlap_result* out /*[host]*/);
+
+/* all ordered pairs of n_clouds handles under cloud->world poses (n_clouds x 16 f64 [host], NULL = all identity):
+ * out[i * n_clouds + j] = ratio of cloud i in cloud j under inv(P_j) * P_i; the diagonal is not computed and is 1.
+ * Argument checks, the pose products on the host and ONE ghicp_overlap_clouds call (NULL poses: with Rt = NULL).  Every handle must be
+ * prepared for thre_dis, because every handle is a target; n_clouds <= 32768; GHICP_ERR_ARG otherwise, `out` untouched.
+ * The pair pose is the RIGID inverse, in f64, with P = [R t; 0 0 0 1] row-major (R[r][c] = P[4 r + c], t[r] = P[4 r + 3]):
+ *   Rt[r][c] = (R_j[0][r] * R_i[0][c] + R_j[1][r] * R_i[1][c]) + R_j[2][r] * R_i[2][c]                         = (R_j^T R_i)[r][c]
+ *   Rt[r][3] = (R_j[0][r] * (t_i[0] - t_j[0]) + R_j[1][r] * (t_i[1] - t_j[1])) + R_j[2][r] * (t_i[2] - t_j[2])  = (R_j^T (t_i - t_j))[r]
+ * every sum of three terms added left to right, no fused multiply-add, bottom row 0 0 0 1; ghicp_overlap_clouds then rounds it to float.
+ * (NOT ghicp_inv_transform, which keeps the reference's negated-translation quirk.) */
+int ghicp_overlap_matrix(ghicp_ctx* ctx, float thre_dis, int32_t n_clouds, const ghicp_cloud* const* clouds, const double* poses,
+                         float* out /*[host] n_clouds x n_clouds*/);
+
+/* ------------------------------------------------------------------------------------------------
  * Pair queue: independent scan pairs sharded over the GPUs of ONE node, one process per GPU (BASELINE configs[3]).
  * The reference registers one pair per process run (test/ghicp_main.cpp:56-160) and has no counterpart; a caller of the drop-in
  * headers that holds MANY pairs shards them with these calls.  Pairs share nothing, so there is NO collective on the data path --
