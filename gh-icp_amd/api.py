@@ -55,7 +55,7 @@ EXPORTS = [
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
     "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
-    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds",
+    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_refine_clouds_reciprocal", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds",
     "ghicp_cloud_prepare_overlap", "ghicp_overlap_clouds", "ghicp_overlap_matrix", "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
     "ghicp_pairqueue_barrier", "ghicp_pairqueue_static_share", "ghicp_pairqueue_claim", "ghicp_pairqueue_counter_reset",
@@ -833,7 +833,7 @@ def _clouds_recompute(self, clouds, xyzs):
     return clouds
 
 
-def _refine_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
+def _refine_clouds(self, params, pairs, Rt_init=None, max_concurrent=0, _entry="ghicp_refine_clouds"):
     """ghicp_refine_clouds: fine ICP of the down-sampled clouds of every (Cloud S, Cloud T) from Rt_init (n x 4 x 4 f64, e.g. the Rt of
     register_clouds; None: identity) in one launch sequence per iteration.  Targets must have been through Cloud.prepare_refine.
     Returns per pair the dict of Context.icp (without the transformed cloud) plus Rt_refined (4,4) f64."""
@@ -846,14 +846,20 @@ def _refine_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
     if Rt_init is not None:
         init = np.ascontiguousarray(Rt_init, dtype=np.float64).reshape(n, 16)
     res = (RefineResult * n)()
-    self._check(self.lib.ghicp_refine_clouds(self.h, C.byref(params), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
-                                             int(max_concurrent), res))
+    self._check(getattr(self.lib, _entry)(self.h, C.byref(params), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
+                                          int(max_concurrent), res))
     out = []
     for r in res:
         d = {k: getattr(r.stats, k) for k, _ in IcpStats._fields_ if k != "pad_"}
         d.update(T=np.array(r.T_icp[:], np.float32).reshape(4, 4), Rt_refined=np.array(r.Rt_refined[:], np.float64).reshape(4, 4))
         out.append(d)
     return out
+
+
+def _refine_clouds_reciprocal(self, params, pairs, inits=None, max_concurrent=0):
+    """ghicp_refine_clouds_reciprocal: Context.refine_clouds with params.use_reciprocal honoured (the reciprocal test of all running pairs
+    of a chunk in one launch sequence per iteration).  Same arguments, same preparation of the targets, same return value."""
+    return _refine_clouds(self, params, pairs, inits, max_concurrent, _entry="ghicp_refine_clouds_reciprocal")
 
 
 def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
@@ -918,6 +924,7 @@ Context.overlap_clouds = _overlap_clouds
 Context.overlap_matrix = _overlap_matrix
 Context.gicp_clouds = _gicp_clouds
 Context.refine_clouds = _refine_clouds
+Context.refine_clouds_reciprocal = _refine_clouds_reciprocal
 Context.clouds_recompute = _clouds_recompute
 Context.cloud_from_features = _cloud_from_features
 Context.register_clouds = _register_clouds

@@ -85,6 +85,10 @@ enum BufSlot {
   // arrays, states, partials and histograms of a chunk reuse the B_ICP_* slots of the single-pair loop)
   // (the batched generalized ICP, refine_gicp.hip, uses the same two and B_GICP_MAHAL for the chunk's Mahalanobis matrices)
   B_RF_DESC, B_RF_MISC,
+  // reciprocal test of the batched fine registration (refine_recip.hip): per-pair ranges / boxes / grids / counters, the back-search's work
+  // lists, the points' indices within their pairs (queries and back-search results reuse B_ICP_Q / B_ICP_NN2 / B_ICP_ND2 of the single-pair
+  // loop, the chunk's source grids the B_GRID2_* slots of its source grid)
+  B_RR_DESC, B_RR_PEND, B_RR_LIDX,
   B_NUM
 };
 
@@ -95,9 +99,10 @@ enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_F
               KT_PAIR_LOOP_DISPATCH,                                         // ONE k_pair_loop dispatch (a class launch of a batch), timed on the stream it runs on -- what rocprofv3's kernel trace reports per row
               KT_REFINE,                                                     // one chunk of the batched fine registration (refine.hip): upload -> final states
               KT_GICP_CLOUDS,                                                // one chunk of the batched generalized ICP (refine_gicp.hip): upload -> final states
+              KT_REFINE_GRID,                                                // inside KT_REFINE: one iteration's source grids of the reciprocal test (refine_recip.hip): boxes -> cell table
               KT_NUM };
 static const char* const kKtNames[KT_NUM] = {"pca_cells", "bsc", "km_solve", "cd_rowmin", "km_weights", "fd_bsc", "nms_round", "voxel_sort",
-                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds"};
+                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds", "refine_recip_grid"};
 
 struct ghicp_ctx {
   // optional per-kernel timing

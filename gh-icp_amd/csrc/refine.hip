@@ -11,39 +11,16 @@
 // blockIdx.y is uniform over the block, so the descriptor reads below are scalar loads, once per block.  A pair that has left its loop is
 // frozen (icp_frozen): its blocks return before they touch anything.  Per iteration the host reads one byte per pair.  No float atomics: the
 // integer counters are those of the single-pair kernels.
+//   ghicp_refine_clouds_reciprocal  the same driver (refine_clouds_impl) with use_reciprocal honoured: after every forward search the reciprocal
+//                               test of all running pairs of the chunk, in one launch sequence and without a host wait (refine_recip.hip)
 #include "cloud.h"
-#include "icp_dev.h"
+#include "refine_dev.h"
 #include "refine_plan.h"
 
 namespace {
 
 using namespace icpdev;
-
-struct RefinePair {
-  NnIndex X;          // the target's grids (buffers of its handle)
-  const float4* tgt;  // the target's down-sampled points
-  const float* tnrm;  // its normals (point-to-plane)
-  const float4* src;  // the source's down-sampled points
-  long long off;      // the pair's slice of the concatenated per-point arrays
-  int ns, pad_;
-  float init[16];     // float(Rt_init)
-};
-
-struct RefineArgs {
-  const RefinePair* pair;
-  IcpState* st;
-  float4* cur;
-  int* nn;
-  float* nd;
-  unsigned* pend;      // work lists of the coarse search, one slice per pair
-  unsigned* pendc;     // their lengths
-  unsigned* ovl;       // calOverlap counts
-  double* part;        // NBLK x NPART per pair
-  unsigned* hist;      // 6 x SEL_BINS per pair
-  unsigned char* flag; // 1: the pair is frozen
-};
-
-constexpr int COARSE_BLK = 512;  // blocks per pair of the coarse search (any count gives the same result: one wave per query)
+using namespace rfdev;
 
 __device__ inline double* part_of(const RefineArgs& A, unsigned p) { return A.part + (size_t)p * NBLK * NPART; }
 __device__ inline unsigned* hist_of(const RefineArgs& A, unsigned p) { return A.hist + (size_t)p * 6 * SEL_BINS; }
@@ -249,24 +226,33 @@ extern "C" int ghicp_cloud_prepare_refine(ghicp_cloud* c, int32_t covariance_k) 
   return GHICP_OK;
 }
 
-extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
-                                   const double* Rt_init, int32_t max_concurrent, ghicp_refine_result* out) {
-  GH_ENTER(ctx);
-  GH_ARG(P != nullptr && n_pairs >= 0 && max_concurrent >= 0 && (n_pairs == 0 || (S != nullptr && T != nullptr && out != nullptr)));
-  GH_ARG(P->metric == GHICP_ICP_POINT_TO_POINT || P->metric == GHICP_ICP_POINT_TO_PLANE);
-  if (P->use_reciprocal) return ctx->fail(GHICP_ERR_ARG, "ghicp_refine_clouds: reciprocal correspondences are not covered by the batch (use ghicp_icp)");
-  if (P->use_trimmed) GH_ARG(P->thre_dis > 0.f);
+namespace {
+
+#define RF_ARG(cond)                                                                   \
+  do {                                                                                 \
+    if (!(cond)) return ctx->fail(GHICP_ERR_ARG, "%s: bad argument (%s)", who, #cond); \
+  } while (0)
+
+// The body of both entry points (`who` names the one that was called).  recip_ok: use_reciprocal is honoured instead of refused.
+int refine_clouds_impl(ghicp_ctx* ctx, const char* who, bool recip_ok, const ghicp_icp_params* P, int32_t n_pairs, const ghicp_cloud* const* S,
+                       const ghicp_cloud* const* T, const double* Rt_init, int32_t max_concurrent, ghicp_refine_result* out) {
+  RF_ARG(P != nullptr && n_pairs >= 0 && max_concurrent >= 0 && (n_pairs == 0 || (S != nullptr && T != nullptr && out != nullptr)));
+  RF_ARG(P->metric == GHICP_ICP_POINT_TO_POINT || P->metric == GHICP_ICP_POINT_TO_PLANE);
+  if (P->use_reciprocal && !recip_ok)
+    return ctx->fail(GHICP_ERR_ARG, "%s: reciprocal correspondences are not covered by this call (use ghicp_refine_clouds_reciprocal or ghicp_icp)", who);
+  const bool recip = P->use_reciprocal != 0;
+  if (P->use_trimmed) RF_ARG(P->thre_dis > 0.f);
   const bool plane = P->metric == GHICP_ICP_POINT_TO_PLANE;
-  if (plane) GH_ARG(P->covariance_k >= 1 && P->covariance_k <= 20);
+  if (plane) RF_ARG(P->covariance_k >= 1 && P->covariance_k <= 20);
   // every pair is checked before anything is written or launched
   std::vector<int64_t> ns_all((size_t)n_pairs);
   for (int i = 0; i < n_pairs; i++) {
     const ghicp_cloud *a = S[i], *b = T[i];
-    GH_ARG(a != nullptr && b != nullptr && a->ctx && b->ctx && a->ctx->device == ctx->device && b->ctx->device == ctx->device);
-    if (!a->ds.p) return ctx->fail(GHICP_ERR_ARG, "ghicp_refine_clouds: the source of pair %d was rebuilt from stored features and holds no points", i);
-    if (!b->rf_ready) return ctx->fail(GHICP_ERR_ARG, "ghicp_refine_clouds: the target of pair %d is not prepared (ghicp_cloud_prepare_refine)", i);
+    RF_ARG(a != nullptr && b != nullptr && a->ctx && b->ctx && a->ctx->device == ctx->device && b->ctx->device == ctx->device);
+    if (!a->ds.p) return ctx->fail(GHICP_ERR_ARG, "%s: the source of pair %d was rebuilt from stored features and holds no points", who, i);
+    if (!b->rf_ready) return ctx->fail(GHICP_ERR_ARG, "%s: the target of pair %d is not prepared (ghicp_cloud_prepare_refine)", who, i);
     if (plane && b->rf_k != P->covariance_k)
-      return ctx->fail(GHICP_ERR_ARG, "ghicp_refine_clouds: the target of pair %d holds normals for k = %d, the parameters ask for k = %d", i, b->rf_k, P->covariance_k);
+      return ctx->fail(GHICP_ERR_ARG, "%s: the target of pair %d holds normals for k = %d, the parameters ask for k = %d", who, i, b->rf_k, P->covariance_k);
     ns_all[i] = a->m;
   }
   if (n_pairs == 0) return GHICP_OK;
@@ -280,7 +266,8 @@ extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, in
     budget = free_b / 2;
   }
 #endif
-  const std::vector<int> bounds = gh_refine_plan(n_pairs, ns_all.data(), max_concurrent, budget);
+  const std::vector<int> bounds = gh_refine_plan(n_pairs, ns_all.data(), max_concurrent, budget, recip ? kRecipPairBytes : kRefinePairBytes,
+                                                 recip ? kRecipPointBytes : kRefinePointBytes);
   std::vector<RefinePair> hd;
   std::vector<IcpState> hs;
   std::vector<unsigned> hovl;
@@ -349,6 +336,8 @@ extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, in
     A.pendc = misc;
     A.ovl = misc + np;
     A.flag = reinterpret_cast<unsigned char*>(misc + 2 * (size_t)np);
+    RecipStage RS;
+    if (recip) GH_TRY(gh_refine_recip_begin(ctx, hd.data(), np, npts, &RS));  // every buffer and the pairs' ranges of the cell table: before the loop
     hipEvent_t kt = ctx->kt_begin(KT_REFINE);
     GH_TRY(ctx->upload_table(hd.data(), (size_t)np * sizeof(RefinePair), dd));
     GH_TRY(ctx->upload_table(hs.data(), (size_t)np * sizeof(IcpState), A.st));
@@ -380,6 +369,7 @@ extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, in
     while (running > 0) {
       if (!have_nn) GH_TRY(nn_search_batch(ctx, A, np, max_gs, 0));
       have_nn = false;
+      if (recip) GH_TRY(gh_refine_recip_step(ctx, A, RS, np, max_gs));  // determineReciprocalCorrespondences: after the search (and the overlap gate)
       hipLaunchKernelGGL(k_rf_corr_count, dim3(max_gs, np), dim3(256), 0, s, A);
       hipLaunchKernelGGL(k_rf_prep, dim3(cdiv(np, 64)), dim3(64), 0, s, A, np);
       if (P->use_trimmed) {
@@ -426,4 +416,18 @@ extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, in
     }
   }
   return GHICP_OK;
+}
+
+}  // namespace
+
+extern "C" int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                                   const double* Rt_init, int32_t max_concurrent, ghicp_refine_result* out) {
+  GH_ENTER(ctx);
+  return refine_clouds_impl(ctx, "ghicp_refine_clouds", false, P, n_pairs, S, T, Rt_init, max_concurrent, out);
+}
+
+extern "C" int ghicp_refine_clouds_reciprocal(ghicp_ctx* ctx, const ghicp_icp_params* P, int32_t n_pairs, const ghicp_cloud* const* S,
+                                              const ghicp_cloud* const* T, const double* Rt_init, int32_t max_concurrent, ghicp_refine_result* out) {
+  GH_ENTER(ctx);
+  return refine_clouds_impl(ctx, "ghicp_refine_clouds_reciprocal", true, P, n_pairs, S, T, Rt_init, max_concurrent, out);
 }

@@ -5,11 +5,18 @@
 #include <cstdint>
 #include <vector>
 
+#include "refine_recip_plan.h"
+
 constexpr int kRefineMaxChunk = 4096;                    // one status byte per pair in the context's 4 KB pinned record
 constexpr size_t kRefinePairBytes = 512 * 32 * 8         // the pair's NBLK partial records
                                     + 6 * 2048 * 4       // its radix-select histograms
                                     + 1024;              // descriptor, state, counters
 constexpr size_t kRefinePointBytes = 16 + 4 + 4 + 4;     // cur, nn, nd, work list of the coarse search -- per source point
+// ghicp_refine_clouds_reciprocal (refine_recip.hip) on top of that, per source point: the query and the back-search's nn / nd / work list, the
+// point's index within its pair; every point enters the sort twice (fine and coarse key): keys and values double-buffered, the sort's spare
+// pair, the points in cell order; the pair's ranges of the cell table (refine_recip_plan.h).  Per pair: the minimum ranges, its boxes and grids.
+constexpr size_t kRecipPointBytes = kRefinePointBytes + 16 + 4 + 4 + 4 + 4 + 2 * (4 * 4) + 2 * (4 + 4) + 2 * 16 + 4 * (kRecipFineCells + kRecipCoarseCells);
+constexpr size_t kRecipPairBytes = kRefinePairBytes + 2 * 4 * kRecipMinCells + 256;
 
 // Chunk boundaries b[0] = 0 < b[1] < ... < b.back() = n_pairs over the pairs in the given order (empty list: {0}).  max_concurrent > 0: chunks of
 // exactly that many pairs (the last one shorter), capped at kRefineMaxChunk.  0: as many pairs per chunk as fit `budget` bytes by the per-pair

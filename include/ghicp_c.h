@@ -479,14 +479,27 @@ typedef struct ghicp_refine_result {
 
 /* S[p] -> T[p] for n_pairs pairs, from Rt_init (n_pairs x 16 row-major f64 [host], the Rt of ghicp_pair_stats; NULL: identity for every
  * pair).  Both metrics, use_trimmed 0 / 1 (with the overlap gate: a refused pair gets done = 0, T_icp = I, Rt_refined = the float-rounded
- * init).  NOT covered: use_reciprocal != 0 -- the reciprocal test needs a grid over the moved source per pair per iteration, a launch
- * sequence per pair; it gets GHICP_ERR_ARG (use ghicp_icp).  GHICP_ERR_ARG also for a target that is not prepared, for point-to-plane
+ * init).  NOT covered by this call: use_reciprocal != 0 -- the reciprocal test needs a grid over the moved source per pair per iteration;
+ * it gets GHICP_ERR_ARG here (use ghicp_refine_clouds_reciprocal below, which builds those grids for a whole chunk at once, or ghicp_icp
+ * pair by pair).  GHICP_ERR_ARG also for a target that is not prepared, for point-to-plane
  * with normals prepared for a k other than params->covariance_k, and for handles of another device; nothing is written then.  The
  * handles are const: nothing is built lazily, so prepared handles may be shared between contexts of the device.
  * max_concurrent: pairs that share one launch sequence (chunks of that size, in the given order; at most 4096); 0: chosen from the free
  * device memory.  Results do not depend on it.  out: n_pairs [host]. */
 int ghicp_refine_clouds(ghicp_ctx* ctx, const ghicp_icp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
                         const double* Rt_init /*[host]*/, int32_t max_concurrent, ghicp_refine_result* out /*[host]*/);
+/* ghicp_refine_clouds with params->use_reciprocal honoured (CRegistration::icp_reg / ptplicp_reg's use_reciprocal_correspondence,
+ * common_reg.cpp:45-107, 122-199).  Arguments, checks, chunking, results and the preparation required of the targets are those of
+ * ghicp_refine_clouds (ghicp_cloud_prepare_refine on targets, nothing extra for sources); the handles are const and nothing is built lazily.
+ * use_reciprocal != 0: pair p comes out as ghicp_cloud_download + ghicp_transform_cloud_f32(source, float(Rt_init[p])) + ghicp_icp with
+ * use_reciprocal = 1 gives it, bit for bit (T_icp, Rt_refined and every field of stats): per iteration the forward search, in a pair's first
+ * iteration the overlap gate from it, then a correspondence i -> j is dropped unless i is the nearest moved source point of target point j
+ * (ties to the lower index), then count / trim / solve; the final fitness search has no reciprocal test.  The grids over the moved sources of
+ * all running pairs of a chunk are built in one launch sequence per iteration, without a host wait, inside cell tables sized before the
+ * loop (about 0.5 KB of device memory per source point of a chunk; max_concurrent = 0 accounts for it).  use_reciprocal == 0: the results of
+ * ghicp_refine_clouds, bit for bit (the same code).  The result of a pair does not depend on the other pairs, their order or max_concurrent. */
+int ghicp_refine_clouds_reciprocal(ghicp_ctx* ctx, const ghicp_icp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                                   const double* Rt_init /*[host]*/, int32_t max_concurrent, ghicp_refine_result* out /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------------
  * Generalized ICP over cached clouds: the loop of ghicp_gicp_from for many pairs of handles at once.  (The reference runs gicp_reg pair
