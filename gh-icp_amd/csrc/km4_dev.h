@@ -93,6 +93,14 @@ struct K4 {
 // to one address are performed in the order it issued them.
 template <bool CP> __device__ inline void k4_gfence() { if (CP) __threadfence_block(); }
 
+// A value every lane of the wave holds alike -- loaded from one LDS or global address, or handed in by the caller -- as ONE copy in a scalar
+// register (v_readfirstlane; f64 as two halves): what is computed from it is scalar arithmetic, a branch on it is a scalar branch instead of
+// an exec-mask region, and it takes no vector register.  Only for values that ARE uniform: the search of k4_dfs and the queue of k4_flood
+// are one wave's work with every lane in step.
+__device__ inline int k4_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ inline unsigned k4_uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ inline double k4_uni(double v) { return __hiloint2double(k4_uni(__double2hiint(v)), k4_uni(__double2loint(v))); }
+
 __device__ inline bool k4_bit(const unsigned* b, int i) { return (b[i >> 5] >> (i & 31)) & 1u; }
 __device__ inline bool k4_flagged(int tn) { return tn > K4_CAP; }
 __device__ inline int k4_cnt(int tn) { return tn > K4_CAP ? 0 : tn; }  // listed entries (0 for flagged rows)
@@ -325,9 +333,9 @@ __device__ inline double k4_wave_min(double v) {
 template <bool PROF, bool CP>
 __device__ inline bool k4_flood(const K4<CP>& s, int qh0, int qt0, double lflood0, int lane, int* qt_out, long long* pc) {
   const int n = s.n;
-  int qh = qh0, qt = qt0;
+  int qh = k4_uni(qh0), qt = k4_uni(qt0);  // queue head and tail, the swept label: wave-uniform (ballot counts, wave minima)
   bool free_l = false;
-  double lflood = lflood0;
+  double lflood = k4_uni(lflood0);
   while (qh < qt) {
     const int qe = qt;
     double lcand = INFINITY;
@@ -359,8 +367,8 @@ __device__ inline bool k4_flood(const K4<CP>& s, int qh0, int qt0, double lflood
         const int l = (int)__ffsll((long long)ob) - 1;
         ob &= ob - 1ull;
         const int xo = __builtin_amdgcn_readlane(xr, l);
-        const double lxo = s.lx[xo];
-        const unsigned cb = s.rptr[xo], ce = s.rptr[xo + 1];
+        const double lxo = k4_uni(s.lx[xo]);
+        const unsigned cb = k4_uni(s.rptr[xo]), ce = k4_uni(s.rptr[xo + 1]);
         for (unsigned c0 = cb; c0 < ce; c0 += 64) {
           const unsigned c = c0 + lane, cc = min(c, ce - 1u);
           const int col = s.cols[cc];
@@ -424,9 +432,11 @@ template <bool PROF, bool CP>
 __device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lane, long long* q_iter, long long* q_act, long long* pd) {
   const int n = s.n;
   const double bg = s.bg, eps = s.eps;
-  int sp = D.sp, x = D.x, ystart = D.ystart;
+  // x, sp, ystart, cnext and everything derived from them (the row's label and entry count, the scan pointer p, best / mbest, the E7 slot)
+  // are wave-uniform: carried in scalar registers; per lane are only the E7 cache (ck, cp) and the window (lc, yw, lyW, mW, visit words)
+  int sp = k4_uni(D.sp), x = k4_uni(D.x), ystart = k4_uni(D.ystart);
   double ck = D.ck;
-  int cp = D.cp, cnext = D.cnext;
+  int cp = D.cp, cnext = k4_uni(D.cnext);
   const int lk = min(lane, K4_CAP - 1);
   for (;;) {
     if (PROF) { ++*q_iter; ++*q_act; }
@@ -438,8 +448,8 @@ __device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lan
     // compiler sinks it back into the flagged branch, and a volatile load is waited for at the loop's back edge: every step then pays a
     // global latency.  47.7 / 72.0 / 38.0 / 342.4 / 57.6 -> 51.6 / 75.0 / 43.0 / 346.7 / 65.7 ms on the five real matrices, mean solve of
     // the bench 44.3 -> 48.3 ms: profiles/r06_km_variants_call3.txt)
-    const double lxv = s.lx[x];
-    const int tn = s.tln[x];
+    const double lxv = k4_uni(s.lx[x]);
+    const int tn = k4_uni((int)s.tln[x]);
     const int lc = s.tlc[x * K4_CAP + lk];
     const int ncnt = k4_cnt(tn);
     const bool bgt = (lxv - bg) < eps;
@@ -466,14 +476,14 @@ __device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lan
     int mW = s.match[ywc];
     int best = INT_MAX, mbest = K4_NONE;
     if (k4_flagged(tn)) {  // flagged row: lowest tight unvisited good column of the CSR row
-      const unsigned cb = s.rptr[x], ce = s.rptr[x + 1];
+      const unsigned cb = k4_uni(s.rptr[x]), ce = k4_uni(s.rptr[x + 1]);
       for (unsigned c0 = cb; c0 < ce; c0 += 64) {
         const unsigned c = c0 + lane, cc = min(c, ce - 1u);
         const int col = s.cols[cc];
         const double val = s.vals[cc];
         const bool t = (int)(c < ce) & (int)(((lxv + s.ly[col]) - val) < eps) & (int)(col >= ystart) & (int)!k4_bit(s.visy, col) & (int)k4_bit(s.goody, col);
         const unsigned long long b = __ballot(t);
-        if (b) { best = __builtin_amdgcn_readlane(col, (int)__ffsll((long long)b) - 1); mbest = s.match[best]; break; }
+        if (b) { best = __builtin_amdgcn_readlane(col, (int)__ffsll((long long)b) - 1); mbest = k4_uni((int)s.match[best]); break; }
       }
     } else {
       const bool t = (int)(lane < ncnt) & (int)(lc >= ystart) & (int)((((~vwL & gwL) >> (lc & 31)) & 1u) != 0u);  // listed = tight (R2)
@@ -567,7 +577,7 @@ __device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lan
       sp--;
       if (sp < 0) return 0;
       k4_gfence<CP>();  // the column lane 0 stored when this frame descended
-      x = s.stx[sp]; ystart = (int)s.sty[sp] + 1;
+      x = k4_uni((int)s.stx[sp]); ystart = k4_uni((int)s.sty[sp]) + 1;
       if (PROF) { pd[4]++; pd[9] += (long long)__builtin_readcyclecounter() - t_it0; }
     }
     __builtin_amdgcn_wave_barrier();
@@ -575,7 +585,7 @@ __device__ inline int k4_dfs(const K4<CP>& s, K4Dfs& D, const bool lazy, int lan
   // augment: match[y] = x on every level of the recursion (km.cpp:26-29); the last column is no longer free
   __builtin_amdgcn_wave_barrier();
   k4_gfence<CP>();
-  const int ylast = s.sty[sp];
+  const int ylast = k4_uni((int)s.sty[sp]);
   for (int f = lane; f <= sp; f += 64) s.match[s.sty[f]] = s.stx[f];
   if (lane == 0) atomicAnd(&s.freey[ylast >> 5], ~(1u << (ylast & 31)));
   return 1;
@@ -695,9 +705,11 @@ __device__ inline bool k4_takes_compact(int n, int flags, int lds_bytes) {
 template <bool PROF, bool CP>
 __device__ inline void k4_solve_block(const Km2Problem& P, int flags, char* smem, int lds_bytes, unsigned long long* __restrict__ lstat, k4_gu16 scr) {
   const unsigned long long t_wall0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;  // 100 MHz, common to all CUs
-  const int n = P.n, nw = (n + 31) / 32, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the descriptor comes out of global memory through vector loads: n, bg and eps as scalars, or every loop bound, every LDS base and every
+  // tightness test that depends on them counts as divergent)
+  const int n = k4_uni(P.n), nw = (n + 31) / 32, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   K4<CP> s;
-  s.n = n; s.nw = nw; s.bg = P.bg; s.eps = P.eps;
+  s.n = n; s.nw = nw; s.bg = k4_uni(P.bg); s.eps = k4_uni(P.eps);
   s.rptr = (k4_gu32)P.row_ptr; s.cols = (k4_gint)P.cols; s.vals = (k4_gf64)P.vals;
   s.lx = (double*)smem;
   s.ly = s.lx + n;

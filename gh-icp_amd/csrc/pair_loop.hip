@@ -176,6 +176,12 @@ __device__ __noinline__ void pl_solve(const LoopProb& P, double* red, int* ired,
   __syncthreads();
 }
 
+// The 100 MHz clock as a scalar: the kernel's time sums then live in scalar registers, not in vector registers that have to survive every stage call.
+__device__ inline unsigned long long pl_now() {
+  const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+  return ((unsigned long long)k4_uni((unsigned)(t >> 32)) << 32) | k4_uni((unsigned)t);
+}
+
 template <int FT, bool PROF>
 __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restrict__ probs, const int* __restrict__ order, const int npairs, int* qhead,
                                                   const int km_flags, const int lds_bytes, unsigned long long* lstat, int* progress,
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
   double* sh = red + 16;
   int* ired = reinterpret_cast<int*>(sh + 32);
   volatile int* s_idx = ired + 18;  // (no static LDS in this kernel: the launch may ask for all 160 KB as dynamic LDS)
-  const unsigned long long t_slot0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const unsigned long long t_slot0 = lstat ? pl_now() : 0ull;
   unsigned long long t_solve = 0ull, t_solve_max = 0ull, n_solve = 0ull, t_sweep = 0ull, t_graph = 0ull, t_tail = 0ull;
   // A slot is one wave's dependent instruction stream for most of its life (the solver's flood and DFS), and in the tail of a batch it
   // shares its SIMD with the throughput kernels of the next batch's front end: behind 7 ALU-bound waves it would get every eighth issue
@@ -209,52 +215,52 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
     __syncthreads();
     if (threadIdx.x == 0) *s_idx = atomicAdd(qh, 1);
     __syncthreads();
-    const int q = *s_idx;
+    const int q = k4_uni((int)*s_idx);  // one value for the workgroup: as a scalar, so that P and what is read through it live in scalar registers across the stage calls
     if (q >= np) break;
     const LoopProb& P = probs[ord[q]];
-    if (threadIdx.x == 0 && lstat) P.st->t_begin = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0 && lstat) P.st->t_begin = pl_now();
     unsigned long long t_pair_max = 0ull;
     int it_pair_max = 0;
-    while (*(volatile int*)&P.st->done == 0) {
+    while (k4_uni(*(volatile int*)&P.st->done) == 0) {  // (a scalar: what the loop carries -- the time sums -- is then not divergent at its exit)
       // GHICP_LOOP_FUSE (mask_all: this launch's membership masks, one region per slot; nullptr: the three passes of before).  The fused stages
       // need whole mask words per column chunk: one chunk, or chunks of CHUNK_MAX columns -- what pick_chunks gives this path.  kpT is staged
       // behind the stage scratch when the slot's LDS holds it.  (Worked out per iteration: nothing of it lives across the stage calls.)
       unsigned* const mask = mask_all ? mask_all + (size_t)blockIdx.x * (size_t)mask_stride : (unsigned*)nullptr;
       const bool fuse = mask != nullptr && (P.C.nchunk_b == 1 || (P.C.chunk_b & 31) == 0);
       double* const sT = PL_KPT_OFF + (long long)P.C.kt * 24 <= (long long)lds_bytes ? reinterpret_cast<double*>(smem + PL_KPT_OFF) : (double*)nullptr;
-      if (lstat) t_sweep -= __builtin_amdgcn_s_memrealtime();
+      if (lstat) t_sweep -= pl_now();
       // calED + calCD_* + sums + penalty (ghicp_reg.cpp:114-139, 216-341), then the sparse graph of findcorrespondenceKM
       // (ghicp_reg.cpp:348-365): count, scan, fill
       if (!fuse) {
         pl_sweep<FT>(P, sB, red);
-        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        if (lstat) { const unsigned long long x = pl_now(); t_sweep += x; t_graph -= x; }
         pl_graph<FT>(P, ired);
-      } else if (FT != GHICP_FEATURE_NONE && *(volatile int*)&P.st->it > 1) {  // the penalty is known before the sweep: membership inside it
+      } else if (FT != GHICP_FEATURE_NONE && k4_uni(*(volatile int*)&P.st->it) > 1) {  // the penalty is known before the sweep: membership inside it
         pl_sweep_km<FT, FT != GHICP_FEATURE_NONE>(P, sB, red, sT, mask);
-        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        if (lstat) { const unsigned long long x = pl_now(); t_sweep += x; t_graph -= x; }
         pl_graph_km<FT, FT != GHICP_FEATURE_NONE>(P, ired, sT, mask);
       } else {
         pl_sweep_km<FT, false>(P, sB, red, sT, mask);
-        if (lstat) { const unsigned long long x = __builtin_amdgcn_s_memrealtime(); t_sweep += x; t_graph -= x; }
+        if (lstat) { const unsigned long long x = pl_now(); t_sweep += x; t_graph -= x; }
         pl_graph_km<FT, false>(P, ired, sT, mask);
       }
-      const unsigned long long t0 = lstat ? __builtin_amdgcn_s_memrealtime() : 0ull;
+      const unsigned long long t0 = lstat ? pl_now() : 0ull;
       // Km::kmsolve (km.cpp:40-126); the layout per pair from its n (scr: this slot's region of the compact layout's global scratch)
       if (k4_takes_compact(P.C.n, km_flags, lds_bytes))
         pl_km_compact<PROF>(P.km_desc, km_flags, smem, lds_bytes, scr ? (k4_gu16)(scr + (size_t)blockIdx.x * (size_t)scr_stride) : (k4_gu16) nullptr);
       else
         pl_km<PROF>(P.km_desc, km_flags, smem, lds_bytes);
       if (lstat) {
-        const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t0;
+        const unsigned long long dt = pl_now() - t0;
         t_graph += t0; t_tail -= t0 + dt;
         t_solve += dt; t_solve_max = dt > t_solve_max ? dt : t_solve_max; n_solve++;
-        if (dt > t_pair_max) { t_pair_max = dt; it_pair_max = *(volatile int*)&P.st->it; }
+        if (dt > t_pair_max) { t_pair_max = dt; it_pair_max = k4_uni(*(volatile int*)&P.st->it); }
       }
       pl_solve<FT>(P, red, ired, sh);  // Km::output, transformestimation, adjustweight (ghicp_reg.cpp:416-460, 605-927)
-      if (lstat) t_tail += __builtin_amdgcn_s_memrealtime();
+      if (lstat) t_tail += pl_now();
     }
     if (threadIdx.x == 0 && lstat) {
-      P.st->t_end = __builtin_amdgcn_s_memrealtime();
+      P.st->t_end = pl_now();
       P.st->t_solve_max = t_pair_max;
       P.st->it_solve_max = it_pair_max;
       // HW_ID (hwreg 4): CU_ID [11:8], SH_ID [12], SE_ID [15:13]; XCC_ID (hwreg 20): [3:0]
@@ -264,7 +270,7 @@ __global__ __launch_bounds__(K4_T, 4) void k_pair_loop(const LoopProb* __restric
   }
   }
   if (threadIdx.x == 0 && lstat) {  // launch record: first slot start, last slot end, sum / max of the solve times, solves, sum of slot lifetimes
-    const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long t1 = pl_now();
     atomicMax(&lstat[0], (1ull << 62) - t_slot0);
     atomicMax(&lstat[1], t1);
     atomicAdd(&lstat[2], t_solve);
