@@ -47,8 +47,10 @@ struct IcpState {
 };
 
 // A pair of a batch that has left its loop -- converged, stopped without correspondences, or refused -- is FROZEN: the single-pair loop
-// stops launching for it, so no block of a batched launch may touch its points, its state or its partial records again.
-__device__ inline bool icp_frozen(const IcpState* st) { return st->refused || st->converged || st->reason == GHICP_ICP_NO_CORRESPONDENCES; }
+// stops launching for it, so no block of a batched launch may touch its points, its state or its partial records again.  One test for
+// both loop states (IcpState; GicpState below: converged, out of iterations, fewer than 4 correspondences, refused).
+template <typename State>
+__device__ inline bool frozen(const State* st) { return st->refused || st->converged || st->reason == GHICP_ICP_NO_CORRESPONDENCES; }
 
 // ------------------------------------------------------------------------------------------------ 1-NN search
 // Rounding margin of axis a: how far beyond the face mn + k * cell a point assigned to cell k may lie.  The cell of a point
@@ -577,9 +579,6 @@ struct GicpState {
   int refused, pad2_;
   double fit_sum;
 };
-
-// A pair of a GICP batch that has left its loop (converged, run out of iterations, fewer than 4 correspondences, refused): see icp_frozen
-__device__ inline bool gicp_frozen(const GicpState* st) { return st->refused || st->converged || st->reason == GHICP_ICP_NO_CORRESPONDENCES; }
 
 constexpr double kGicpStop = 1e-10;  // N8: the inner loop stops once max |dx| < this
 

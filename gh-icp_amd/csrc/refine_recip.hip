@@ -23,9 +23,10 @@
 //   k_rr_kill                 nn[i] = -1 where the back-search does not return i; nd stays
 // Two grids per pair (fine + coarse), as ghicp_icp builds: a query far from the moved source (the target point an outlier chose) costs a
 // bounded number of cells.  A single grid would save half the sort; the two have not been measured against each other.
-// A frozen pair (icp_frozen) takes no part: its blocks return before the box, the plan, the query, the searches and the kill.  Its points
+// A frozen pair (icpdev::frozen) takes no part: its blocks return before the box, the plan, the query, the searches and the kill.  Its points
 // ride along in the sort under the first key of the pair's own ranges, where no search looks: nothing of the pair is written.
-// blockIdx.y is the pair and uniform over the block: the descriptor reads are scalar loads.  No float atomics.
+// blockIdx.y is the pair and uniform over the block: the descriptor reads are scalar loads.  No float atomics.  These kernels spell the 2-D
+// prologue out: with point_block / coarse_blocks of refine_dev.h (the forward loop's form) this stage measured 0.6 % slower.
 #include "prims.h"
 #include "refine_dev.h"
 
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void k_rr_box(RefineArgs A, RecipStage R) {
   const unsigned p = blockIdx.y;
   const RefinePair& D = A.pair[p];
   if (blockIdx.x * 256u >= (unsigned)D.ns) return;
-  if (icp_frozen(&A.st[p])) return;
+  if (frozen(&A.st[p])) return;
   __shared__ float smin[3][4], smax[3][4];
   const float4* cur = A.cur + D.off;
   float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
@@ -84,7 +85,7 @@ __device__ inline GridDesc desc_of(const RecipGrid& g, int n) {
 
 __global__ __launch_bounds__(64) void k_rr_plan(RefineArgs A, RecipStage R, int np) {
   const int p = blockIdx.x * 64 + threadIdx.x;
-  if (p >= np || icp_frozen(&A.st[p])) return;
+  if (p >= np || frozen(&A.st[p])) return;
   float mm[6];
   for (int k = 0; k < 6; k++) mm[k] = ord_dec(R.box[p * 6 + k]);
   const RecipRange rg = R.range[p];
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void k_rr_keys(RefineArgs A, RecipStage R) {
   const RecipRange rg = R.range[p];
   const long long gi = D.off + i;
   unsigned kf = rg.base_f, kc = rg.base_c;  // a frozen pair: the first cell of its own ranges
-  if (!icp_frozen(&A.st[p])) {
+  if (!frozen(&A.st[p])) {
     const float4 P = A.cur[gi];
     kf += cell_key(R.grid[2 * p], P);
     kc += cell_key(R.grid[2 * p + 1], P);
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void k_rr_query(RefineArgs A, RecipStage R) { 
   const unsigned p = blockIdx.y;
   const RefinePair& D = A.pair[p];
   if (blockIdx.x * 256u >= (unsigned)D.ns) return;
-  if (icp_frozen(&A.st[p])) return;
+  if (frozen(&A.st[p])) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < D.ns) R.q[D.off + i] = D.tgt[max(A.nn[D.off + i], 0)];
 }
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void k_rr_nn_fine(RefineArgs A, RecipStage R) 
   const unsigned p = blockIdx.y;
   const RefinePair& D = A.pair[p];
   if (blockIdx.x * 256u >= (unsigned)D.ns) return;
-  if (icp_frozen(&A.st[p])) return;
+  if (frozen(&A.st[p])) return;
   nn_fine_body(source_grid(R, p, 0), R.q + D.off, D.ns, blockIdx.x * 256 + threadIdx.x, R.nn2 + D.off, R.nd2 + D.off, R.pend2 + D.off, &R.pendc2[p]);
 }
 
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(256) void k_rr_nn_coarse(RefineArgs A, RecipStage R
   const RefinePair& D = A.pair[p];
   const unsigned nb = (unsigned)min(cdiv_dev(D.ns, 4), COARSE_BLK);
   if (blockIdx.x >= nb) return;
-  if (icp_frozen(&A.st[p])) return;
+  if (frozen(&A.st[p])) return;
   nn_coarse_body(source_grid(R, p, 1), R.q + D.off, R.pend2 + D.off, R.pendc2[p], blockIdx.x * 4u + (threadIdx.x >> 6), nb * 4u, R.nn2 + D.off, R.nd2 + D.off);
 }
 
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void k_rr_kill(RefineArgs A, RecipStage R) {  
   const unsigned p = blockIdx.y;
   const RefinePair& D = A.pair[p];
   if (blockIdx.x * 256u >= (unsigned)D.ns) return;
-  if (icp_frozen(&A.st[p])) return;
+  if (frozen(&A.st[p])) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < D.ns && R.nn2[D.off + i] != i) A.nn[D.off + i] = -1;
 }

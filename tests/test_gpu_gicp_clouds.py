@@ -13,7 +13,7 @@ import pytest
 
 import gicp_restatement as G
 from conftest import rot_err, trans_err
-from test_gpu_refine import STAT_KEYS, World, displaced
+from test_gpu_refine import STAT_KEYS, World, displaced, lattice
 from test_gpu_refine import params_of as icp_params_of
 from test_icp_cpu import small_pair
 
@@ -224,14 +224,6 @@ def test_multiview_a_refused_pair_leaves_its_neighbours_alone(world):
 
 
 # ------------------------------------------------------------------------------------------------ 4. edges of the 2-D launch
-def lattice(n, seed):
-    """n points 0.5 m apart with +-0.1 m of jitter: no two share a 0.2 m voxel, so the handle's m is n."""
-    rng = np.random.default_rng(seed)
-    side = int(np.ceil(n ** (1.0 / 3.0)))
-    g = np.stack(np.meshgrid(*([np.arange(side)] * 3), indexing="ij"), -1).reshape(-1, 3)[:n]
-    return (g * 0.5 + rng.uniform(-0.1, 0.1, (n, 3))).astype(np.float32)
-
-
 def test_edges_of_the_two_dimensional_launch(ctx, api):
     cfg = api.pair_config(api.FEATURE_NONE, api.CORR_NN, dof=6, voxel=0.2, max_iter=10)
     tgt = lattice(3000, 1)

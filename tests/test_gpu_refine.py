@@ -231,3 +231,69 @@ def test_prepare_again_and_after_recompute(world, ctx, api):
         assert_same_results(got, first)
     finally:
         h.close()
+
+
+def lattice(n, seed):
+    """n points 0.5 m apart with +-0.1 m of jitter: no two share a 0.2 m voxel, so the handle's m is n (test_gpu_gicp_clouds.py uses it too)."""
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(n ** (1.0 / 3.0)))
+    g = np.stack(np.meshgrid(*([np.arange(side)] * 3), indexing="ij"), -1).reshape(-1, 3)[:n]
+    return (g * 0.5 + rng.uniform(-0.1, 0.1, (n, 3))).astype(np.float32)
+
+
+def edge_raws():
+    """Sources at the edges of the 2-D launch over one lattice target: fewer than 4 points; one block; just into a second block of 256; a
+    second block of the radix select (cdiv(ns, 2048)).  A fifth of every source lies 9 m to the side, beyond the target (its lattice spans
+    7 m): the overlap stays below 1, so the trimmed rejector and its select are at work; the initial pose is a little off the one the sources
+    were made with, so the loop has something to do.  Returns the four sources, the target and the initial pose."""
+    tgt = lattice(3000, 1)
+    made = displaced(np.eye(4), 0.3, (0.03, -0.02, 0.01))
+    inv = np.linalg.inv(made)
+    rng = np.random.default_rng(2)
+    raws = []
+    for n in (2, 100, 257, 2500):
+        x = tgt[rng.permutation(len(tgt))[:n]].astype(np.float64)
+        x[: n // 5, 0] += 9.0
+        raws.append((x @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32))
+    return raws, tgt, displaced(made, 0.2, (0.02, 0.01, -0.01))
+
+
+@pytest.fixture(scope="module")
+def edge_clouds(ctx, api):
+    """edge_raws as prepared handles.  The voxel filter keeps its first input point once more unless a point falls into the corner voxel, so m
+    is n or n + 1: the classes are asserted on the m the handles report."""
+    cfg = api.pair_config(api.FEATURE_NONE, api.CORR_NN, dof=6, voxel=0.2, max_iter=10)
+    raws, tgt, init = edge_raws()
+    clouds = [ctx.cloud_create(cfg, x) for x in raws + [tgt]]
+    ms = [int(c.info().m) for c in clouds]
+    print("down-sampled sizes:", ms)
+    assert ms[0] < 4 and 4 <= ms[1] <= 256 and 257 <= ms[2] <= 258 and ms[3] > 2048 and ms[4] > 2048
+    for c in clouds:
+        c.prepare_refine(K)
+    yield clouds, ms, init, [c.download()["ds"] for c in clouds]
+    for c in clouds:
+        c.close()
+
+
+@pytest.mark.parametrize("metric,trimmed", [(0, True), (1, False)])
+def test_edges_of_the_two_dimensional_launch(ctx, api, edge_clouds, metric, trimmed):
+    clouds, ms, init, ds = edge_clouds
+    prm = params_of(api, metric, trimmed, max_iter=3)
+    T = clouds[4]
+    # the small pairs sit between and after large ones: the blocks beyond their cdiv(ns, 256), min(cdiv(ns, 4), 512) and cdiv(ns, 2048) must do nothing
+    order = [3, 0, 1, 3, 2, 0]
+    inits = np.stack([init] * len(order))
+    got = ctx.refine_clouds(prm, [(clouds[i], T) for i in order], inits)
+    ref = {i: ctx.icp(ctx.transform_cloud_f32(ds[i], init.astype(np.float32)), ds[4], prm, want_transformed=False) for i in set(order)}
+    for i, g in zip(order, got):
+        r = ref[i]
+        for k in STAT_KEYS:
+            assert g[k] == r[k], (ms[i], k, g[k], r[k])
+        assert r["done"] == 1
+        np.testing.assert_array_equal(g["T"], r["T"])
+        np.testing.assert_array_equal(g["Rt_refined"], product_f64(g["T"], init))
+    print("iterations:", [g["iterations"] for g in got], "reasons:", [g["reason"] for g in got], "correspondences:", [g["correspondences"] for g in got])
+    assert all(g["iterations"] >= 1 for i, g in zip(order, got) if i != 0)  # the pairs above the minimum went through the loop
+    if trimmed:
+        assert all(0.0 < g["overlap"] < 1.0 for i, g in zip(order, got) if i != 0), [g["overlap"] for g in got]
+    assert_same_results(ctx.refine_clouds(prm, [(clouds[i], T) for i in order], inits, 2), got)
