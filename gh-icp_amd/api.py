@@ -56,7 +56,9 @@ EXPORTS = [
     "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
     "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_refine_clouds_reciprocal", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds",
-    "ghicp_cloud_prepare_overlap", "ghicp_overlap_clouds", "ghicp_overlap_matrix", "ghicp_sbf_write", "ghicp_sbf_read",
+    "ghicp_cloud_prepare_overlap", "ghicp_overlap_clouds", "ghicp_overlap_matrix",
+    "ghicp_prepare_spec_default", "ghicp_clouds_prepare", "ghicp_ctx_prepare_host_waits", "ghicp_cloud_get_prepared", "ghicp_cloud_download_prepared",
+    "ghicp_sbf_write", "ghicp_sbf_read",
     "ghicp_pairqueue_create", "ghicp_pairqueue_destroy", "ghicp_pairqueue_last_error", "ghicp_pairqueue_info", "ghicp_pairqueue_broadcast",
     "ghicp_pairqueue_barrier", "ghicp_pairqueue_static_share", "ghicp_pairqueue_claim", "ghicp_pairqueue_counter_reset",
     "ghicp_pairqueue_gather_records", "ghicp_pairqueue_pack_records", "ghicp_pairqueue_register_pairs",
@@ -727,6 +729,26 @@ class CloudInfo(C.Structure):
                 ("bbx_magnitude", C.c_float), ("candidates", C.c_int32), ("feature_bytes", C.c_int64)]
 
 
+class PrepareSpec(C.Structure):
+    """ghicp_prepare_spec: what ghicp_clouds_prepare builds for every handle of its list."""
+    _fields_ = [("refine", C.c_int32), ("normals_k", C.c_int32), ("gicp_k", C.c_int32), ("overlap", C.c_int32), ("thre_dis", C.c_float),
+                ("pad_", C.c_int32), ("gicp_epsilon", C.c_double)]
+
+
+class GridInfo(C.Structure):
+    _fields_ = [("mn", C.c_float * 3), ("inv", C.c_float), ("dim", C.c_int32 * 3), ("n", C.c_int32), ("ncell", C.c_uint32), ("pad_", C.c_int32)]
+
+
+class CloudPrepared(C.Structure):
+    _fields_ = [("refine_ready", C.c_int32), ("normals_k", C.c_int32), ("gicp_ready", C.c_int32), ("gicp_k", C.c_int32),
+                ("overlap_ready", C.c_int32), ("pad_", C.c_int32), ("thre_dis", C.c_float), ("pad2_", C.c_float), ("gicp_epsilon", C.c_double),
+                ("fine", GridInfo), ("coarse", GridInfo), ("overlap", GridInfo)]
+
+
+(PREP_FINE_PTS, PREP_FINE_START, PREP_COARSE_PTS, PREP_COARSE_START, PREP_OVERLAP_PTS, PREP_OVERLAP_START, PREP_NORMALS,
+ PREP_COVARIANCES) = range(8)
+
+
 class Cloud:
     """A ghicp_cloud handle: the down-sampled points, keypoints and descriptors of one cloud, resident in HBM."""
 
@@ -775,6 +797,29 @@ class Cloud:
         Needed again after every recompute."""
         self.ctx._check(self.ctx.lib.ghicp_cloud_prepare_overlap(self.h, C.c_float(thre_dis)))
         return self
+
+    def prepared(self) -> "CloudPrepared":
+        """ghicp_cloud_get_prepared: which prepared state the handle holds, and the descriptors of its grids."""
+        p = CloudPrepared()
+        self.ctx._check(self.ctx.lib.ghicp_cloud_get_prepared(self.h, C.byref(p)))
+        return p
+
+    def download_prepared(self, which):
+        """ghicp_cloud_download_prepared: one part of the prepared state as a device tensor.  which: a PREP_* constant.  *_PTS (m, 4) f32
+        (w = the bits of the point's index), *_START (ncell + 1,) int32 holding the u32 values, normals (m, 3) f32, covariances (m, 6) f64.
+        GhicpError when the handle does not hold that part."""
+        t, c, m, p = self.ctx.torch, self.ctx, self.info().m, self.prepared()
+        if which in (PREP_FINE_PTS, PREP_COARSE_PTS, PREP_OVERLAP_PTS):
+            out = t.empty((m, 4), dtype=t.float32, device=c.dev)
+        elif which in (PREP_FINE_START, PREP_COARSE_START, PREP_OVERLAP_START):
+            g = {PREP_FINE_START: p.fine, PREP_COARSE_START: p.coarse, PREP_OVERLAP_START: p.overlap}[which]
+            out = t.empty((g.ncell + 1 if m > 0 else 0,), dtype=t.int32, device=c.dev)
+        elif which == PREP_NORMALS:
+            out = t.empty((m, 3), dtype=t.float32, device=c.dev)
+        else:
+            out = t.empty((m, 6), dtype=t.float64, device=c.dev)
+        c._check(c.lib.ghicp_cloud_download_prepared(self.h, int(which), _ptr(out) if out.numel() > 0 else None))
+        return out
 
     def close(self):
         if self.h:
@@ -919,6 +964,30 @@ def _overlap_matrix(self, clouds, thre_dis, poses=None):
     return out
 
 
+def _prepare_clouds(self, clouds, refine=False, normals_k=0, gicp_k=0, gicp_eps=1e-3, overlap_thre=None):
+    """ghicp_clouds_prepare: for every Cloud of the list, in one launch sequence per chunk, the state Cloud.prepare_refine(normals_k)
+    (refine or normals_k > 0), Cloud.prepare_gicp(gicp_k, gicp_eps) (gicp_k > 0) and Cloud.prepare_overlap(overlap_thre) (not None) leave,
+    in this order, bit for bit.  Returns the list."""
+    n = len(clouds)
+    spec = PrepareSpec()
+    self._check(self.lib.ghicp_prepare_spec_default(C.byref(spec)))
+    spec.refine, spec.normals_k, spec.gicp_k, spec.gicp_epsilon = int(bool(refine)), int(normals_k), int(gicp_k), float(gicp_eps)
+    if overlap_thre is not None:
+        spec.overlap, spec.thre_dis = 1, float(overlap_thre)
+    H = (C.c_void_p * max(n, 1))(*[c.h.value if c is not None else None for c in clouds])
+    self._check(self.lib.ghicp_clouds_prepare(self.h, n, H, C.byref(spec)))
+    return clouds
+
+
+def _prepare_host_waits(self):
+    """Host waits (stream synchronisations) of this context's last prepare_clouds."""
+    w = C.c_int64(0)
+    self._check(self.lib.ghicp_ctx_prepare_host_waits(self.h, C.byref(w)))
+    return w.value
+
+
+Context.prepare_clouds = _prepare_clouds
+Context.prepare_host_waits = _prepare_host_waits
 Context.cloud_create = _cloud_create
 Context.overlap_clouds = _overlap_clouds
 Context.overlap_matrix = _overlap_matrix

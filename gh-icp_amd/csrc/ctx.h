@@ -89,6 +89,10 @@ enum BufSlot {
   // lists, the points' indices within their pairs (queries and back-search results reuse B_ICP_Q / B_ICP_NN2 / B_ICP_ND2 of the single-pair
   // loop, the chunk's source grids the B_GRID2_* slots of its source grid)
   B_RR_DESC, B_RR_PEND, B_RR_LIDX,
+  // batched prepare (prepare_clouds.hip): descriptor tables of the passes, boxes / occupied-cell counters, the chunk's concatenated clouds
+  // (all of them; those of a k-NN pass), the k-NN pass's normals and covariances before they go to the handles (the sorts and cell tables
+  // of a chunk reuse the B_GRID_* / B_GRID2_* slots, the neighbour lists the B_FE_SORTK / B_FE_SORTK2 / B_FE_COUNT slots of the single-cloud calls)
+  B_PP_DESC, B_PP_BOX, B_PP_CAT, B_PP_CATK, B_PP_NRM, B_PP_COV,
   B_NUM
 };
 
@@ -100,9 +104,10 @@ enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_F
               KT_REFINE,                                                     // one chunk of the batched fine registration (refine.hip): upload -> final states
               KT_GICP_CLOUDS,                                                // one chunk of the batched generalized ICP (refine_gicp.hip): upload -> final states
               KT_REFINE_GRID,                                                // inside KT_REFINE: one iteration's source grids of the reciprocal test (refine_recip.hip): boxes -> cell table
+              KT_PP_GRIDS, KT_PP_KNN,                                        // one chunk of the batched prepare (prepare_clouds.hip): the grids that go into the handles; the k-NN passes (grid, search, normals / covariances)
               KT_NUM };
 static const char* const kKtNames[KT_NUM] = {"pca_cells", "bsc", "km_solve", "cd_rowmin", "km_weights", "fd_bsc", "nms_round", "voxel_sort",
-                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds", "refine_recip_grid"};
+                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds", "refine_recip_grid", "prepare_grids", "prepare_knn"};
 
 struct ghicp_ctx {
   // optional per-kernel timing
@@ -249,6 +254,8 @@ struct ghicp_ctx {
     return GHICP_OK;
   }
   void* fb_pinned = nullptr;  // descriptor block + report of the batched front end (batch.hip)
+  void* pp_pinned = nullptr;  // descriptor tables + counters of the batched prepare (prepare_clouds.hip)
+  long long pp_waits = 0;     // host waits of the last ghicp_clouds_prepare (ghicp_ctx_prepare_host_waits)
   std::vector<struct ghicp_cloud*> pair_clouds;  // cloud handles behind ghicp_register_pairs (2 per pair slot; cloud.hip)
   size_t pinned_cap = 0;
   int num_cu = 256;

@@ -67,6 +67,7 @@ extern "C" int ghicp_ctx_destroy(ghicp_ctx* ctx) {
   if (ctx->job_pinned) (void)hipHostFree(ctx->job_pinned);
   if (ctx->job_event) (void)hipEventDestroy(ctx->job_event);
   if (ctx->fb_pinned) (void)hipHostFree(ctx->fb_pinned);
+  if (ctx->pp_pinned) (void)hipHostFree(ctx->pp_pinned);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   for (auto& e : ctx->confine_cache) { (void)hipStreamDestroy(e.confined); (void)hipStreamDestroy(e.rest); }
   for (hipStream_t a : ctx->aux_streams) (void)hipStreamDestroy(a);

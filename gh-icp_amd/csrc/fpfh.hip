@@ -381,6 +381,27 @@ int gh_gicp_cov_dev(ghicp_ctx* ctx, const float* xyz, long long m, int stride, i
   return GHICP_OK;
 }
 
+// Both of the above for the concatenated clouds of a batch (ghicp_clouds_prepare, prepare_clouds.hip, builds the batch's k-NN grid as
+// batch.hip does): ONE search, then the normals (CheckNormals applied) and / or the covariances over the same lists -- the kernels of the
+// single-cloud calls, so row i of a cloud comes out as gh_knn_normals_dev / gh_gicp_cov_dev give it for that cloud alone.
+int gh_knn_prepare_batch_dev(ghicp_ctx* ctx, const float4* dsg, int M, const float4* pts, const unsigned* start, const GridDesc* gd_dev,
+                             const unsigned* cell_base_dev, const int* moff_dev, int nb, int k, float* normals, double eps, double* cov6) {
+  if (M <= 0) return GHICP_OK;
+  if (k < 1 || k > KNN) return ctx->fail(GHICP_ERR_ARG, "batched k-NN: k must be in [1, %d]", KNN);
+  hipStream_t s = ctx->stream;
+  int *nn, *nk;
+  float* nd;
+  GH_TRY(ctx->reserve(B_FE_SORTK, (size_t)M * KNN + 1, &nn));
+  GH_TRY(ctx->reserve(B_FE_SORTK2, (size_t)M * KNN + 1, &nd));
+  GH_TRY(ctx->reserve(B_FE_COUNT, (size_t)M + 1, &nk));
+  const float* xyz = reinterpret_cast<const float*>(dsg);
+  hipLaunchKernelGGL(k_knn_batch, dim3(cdiv(M, 128)), dim3(128), 0, s, pts, start, gd_dev, cell_base_dev, moff_dev, nb, M, k, nn, nd, nk);
+  if (normals) hipLaunchKernelGGL(k_normals, dim3(cdiv(M, 256)), dim3(256), 0, s, xyz, 4, (long long)M, nn, nk, normals, 1);
+  if (cov6) hipLaunchKernelGGL(k_gicp_cov, dim3(cdiv(M, 256)), dim3(256), 0, s, xyz, 4, (long long)M, nn, nk, eps, cov6);
+  GH_HIP(hipGetLastError());
+  return GHICP_OK;
+}
+
 int gh_gather_rows33_dev(ghicp_ctx* ctx, const float* hist, const int32_t* idx, long long k, float* out) {
   if (k <= 0) return GHICP_OK;
   hipLaunchKernelGGL(k_gather_rows33, dim3(cdiv(k * 33, 256)), dim3(256), 0, ctx->stream, hist, idx, k, out);

@@ -15,6 +15,8 @@ int gh_gather_rows33_dev(ghicp_ctx* ctx, const float* hist, const int32_t* idx, 
 float gh_fpfh_cell(const float* mm, long long m);  // fpfh.hip: the cell size of the k-NN grid of one cloud
 int gh_fpfh_batch_dev(ghicp_ctx* ctx, const float4* dsg, int M, const float4* pts, const unsigned* start, const GridDesc* gd_dev, const unsigned* cell_base_dev,
                       const int* moff_dev, int nb, float* hist);  // fpfh.hip
+int gh_knn_prepare_batch_dev(ghicp_ctx* ctx, const float4* dsg, int M, const float4* pts, const unsigned* start, const GridDesc* gd_dev,
+                             const unsigned* cell_base_dev, const int* moff_dev, int nb, int k, float* normals, double eps, double* cov6);  // fpfh.hip
 int gh_fd_fpfh_dev(ghicp_ctx* ctx, const float* histS, int ks, const float* histT, int kt, float* FD);  // fd.hip
 int gh_register_pairs_batched(ghicp_ctx* ctx, const ghicp_pair_config* cfg, int32_t n_pairs, const float* const* xyzS, const int64_t* nS,
                               const float* const* xyzT, const int64_t* nT, int stride, ghicp_pair_stats* stats, int* handled);  // cloud.hip

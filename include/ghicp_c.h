@@ -574,6 +574,60 @@ int ghicp_overlap_matrix(ghicp_ctx* ctx, float thre_dis, int32_t n_clouds, const
                          float* out /*[host] n_clouds x n_clouds*/);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batched prepare: what ghicp_cloud_prepare_refine / ghicp_cloud_prepare_gicp / ghicp_cloud_prepare_overlap build cloud by cloud, for MANY
+ * handles in one launch sequence per chunk -- every recompute invalidates the prepared state, so a streaming caller pays for it with every
+ * batch of scans.  (The reference builds its kd-trees, normals and covariances inside every icp_reg / ptplicp_reg / gicp_reg call; it has
+ * no counterpart.)
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct ghicp_prepare_spec {
+  int32_t refine;       /* != 0: fine + coarse 1-NN grids (ghicp_cloud_prepare_refine) */
+  int32_t normals_k;    /* 0..20; > 0 implies refine: the k-NN normals of ghicp_cloud_prepare_refine(c, normals_k) */
+  int32_t gicp_k;       /* 0: none; 1..20 implies refine: the covariances of ghicp_cloud_prepare_gicp(c, gicp_k, gicp_epsilon) */
+  int32_t overlap;      /* != 0: the grid of ghicp_cloud_prepare_overlap(c, thre_dis) */
+  float   thre_dis;     /* > 0 when overlap */
+  int32_t pad_;
+  double  gicp_epsilon; /* > 0 when gicp_k */
+} ghicp_prepare_spec;
+/* all zero, gicp_epsilon 1e-3, thre_dis 0.5; GHICP_ERR_ARG for NULL */
+int ghicp_prepare_spec_default(ghicp_prepare_spec* s);
+/* After the call every handle of the list is in exactly the state these per-cloud calls leave, made in this order, bit for bit (every
+ * descriptor, every buffer):
+ *   1. ghicp_cloud_prepare_refine(c, normals_k)        when refine != 0 or normals_k > 0
+ *   2. ghicp_cloud_prepare_gicp(c, gicp_k, gicp_epsilon) when gicp_k > 0  (it builds the 1-NN grids itself when the handle holds none; alone it
+ *                                                      leaves the normals and their k as they are, as the per-cloud call does)
+ *   3. ghicp_cloud_prepare_overlap(c, thre_dis)        when overlap != 0
+ * with their keep / replace rules: state held for the same parameters is not rebuilt, another k replaces the normals and keeps the grids,
+ * normals_k = 0 with refine keeps the normals' buffer and sets their k to 0, and so on.  A handle's result depends neither on the other
+ * handles of the list nor on their order.  The list goes through in chunks of at most 64 clouds (fewer when the points of a chunk would
+ * reach 2^31 - 2 or the cells of one of its grids 2^28); per chunk ONE launch sequence, and host waits whose number does not grow with the
+ * clouds of the chunk: one for the bounding boxes of the whole list, one per halving round of the fine cell (at most five, for all clouds
+ * still halving), one at the end.  One k-NN search serves normals and covariances when normals_k == gicp_k; otherwise two searches run.
+ * Handles are synchronised on return and may then serve any context of the device.
+ * Every handle and the spec are checked before anything is touched or launched; GHICP_ERR_ARG then leaves every handle as it was: a NULL
+ * handle, a handle listed twice, a handle rebuilt by ghicp_cloud_from_features, a handle of another context than ctx (the rule of
+ * ghicp_clouds_recompute), normals_k or gicp_k outside 0..20, thre_dis <= 0 with overlap, gicp_epsilon <= 0 with gicp_k.  n_clouds == 0 or
+ * a spec that asks for nothing: GHICP_OK, nothing happens.  In host-pointer mode the per-cloud calls run one after the other. */
+int ghicp_clouds_prepare(ghicp_ctx* ctx, int32_t n_clouds, ghicp_cloud* const* clouds /*[host]*/, const ghicp_prepare_spec* spec);
+/* host waits (stream synchronisations) of the last ghicp_clouds_prepare of this context */
+int ghicp_ctx_prepare_host_waits(const ghicp_ctx* ctx, int64_t* waits);
+
+/* Reading the prepared state back: the normals and covariances of the down-sampled cloud without computing them again, and how the two
+ * ways of preparing are compared. */
+typedef struct ghicp_grid_info { float mn[3]; float inv; int32_t dim[3]; int32_t n; uint32_t ncell; int32_t pad_; } ghicp_grid_info;
+typedef struct ghicp_cloud_prepared {
+  int32_t refine_ready, normals_k, gicp_ready, gicp_k, overlap_ready, pad_;
+  float thre_dis, pad2_; double gicp_epsilon;
+  ghicp_grid_info fine, coarse, overlap;           /* zeroed when not held */
+} ghicp_cloud_prepared;
+int ghicp_cloud_get_prepared(const ghicp_cloud* cloud, ghicp_cloud_prepared* out /*[host]*/);
+enum { GHICP_PREP_FINE_PTS, GHICP_PREP_FINE_START, GHICP_PREP_COARSE_PTS, GHICP_PREP_COARSE_START,
+       GHICP_PREP_OVERLAP_PTS, GHICP_PREP_OVERLAP_START, GHICP_PREP_NORMALS, GHICP_PREP_COVARIANCES };
+/* *_PTS: m x 4 f32 in cell order (w = the bits of the point's index in the down-sampled cloud, copied as bytes); *_START: ncell + 1 u32;
+ * normals m x 3 f32; covariances m x 6 f64.  `out` follows the context's pointer mode, like ghicp_cloud_download.  GHICP_ERR_ARG when that
+ * part is not held (normals: prepared with k = 0). */
+int ghicp_cloud_download_prepared(const ghicp_cloud* cloud, int32_t which, void* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Pair queue: independent scan pairs sharded over the GPUs of ONE node, one process per GPU (BASELINE configs[3]).
  * The reference registers one pair per process run (test/ghicp_main.cpp:56-160) and has no counterpart; a caller of the drop-in
  * headers that holds MANY pairs shards them with these calls.  Pairs share nothing, so there is NO collective on the data path --
