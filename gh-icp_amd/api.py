@@ -53,9 +53,9 @@ EXPORTS = [
     "ghicp_rigid_svd", "ghicp_rigid_svd_host", "ghicp_register", "ghicp_loop_create", "ghicp_iterate", "ghicp_loop_result", "ghicp_loop_destroy", "ghicp_transform_cloud", "ghicp_transform_clouds", "ghicp_register_pair",
     "ghicp_register_pairs",
     "ghicp_icp_params_default", "ghicp_cal_overlap", "ghicp_icp", "ghicp_knn_normals", "ghicp_nn_search", "ghicp_inv_transform",
-    "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_covariances",
+    "ghicp_transform_cloud_f32", "ghicp_gicp_params_default", "ghicp_gicp", "ghicp_gicp_from", "ghicp_gicp_trimmed_from", "ghicp_gicp_covariances",
     "ghicp_cloud_create", "ghicp_cloud_recompute", "ghicp_clouds_recompute", "ghicp_cloud_from_features", "ghicp_cloud_destroy", "ghicp_cloud_get_info", "ghicp_cloud_download",
-    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_refine_clouds_reciprocal", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds",
+    "ghicp_register_clouds", "ghicp_cloud_prepare_refine", "ghicp_refine_clouds", "ghicp_refine_clouds_reciprocal", "ghicp_cloud_prepare_gicp", "ghicp_gicp_clouds", "ghicp_gicp_clouds_trimmed",
     "ghicp_cloud_prepare_overlap", "ghicp_overlap_clouds", "ghicp_overlap_matrix",
     "ghicp_prepare_spec_default", "ghicp_clouds_prepare", "ghicp_ctx_prepare_host_waits", "ghicp_cloud_get_prepared", "ghicp_cloud_download_prepared",
     "ghicp_sbf_write", "ghicp_sbf_read",
@@ -658,9 +658,11 @@ class Context:
         d.update(T=T.reshape(4, 4), transformed=out)
         return d
 
-    def gicp(self, xyzS, xyzT, params: GicpParams, want_transformed=True, guess=None):
+    def gicp(self, xyzS, xyzT, params: GicpParams, want_transformed=True, guess=None, trim_ratio=None):
         """gicp_reg.  Returns the dict of icp(): done, T (4,4) f32, transformed tensor, + ghicp_icp_stats fields.  guess: (4,4) initial
-        source->target pose (ghicp_gicp_from; T is then the total pose, guess included); None: ghicp_gicp."""
+        source->target pose (ghicp_gicp_from; T is then the total pose, guess included); None: ghicp_gicp.  trim_ratio: None, or the share
+        of the correspondences every outer iteration keeps (ghicp_gicp_trimmed_from: in (0, 1], or 0 for the gate's overlap estimate, which
+        needs params.use_trimmed)."""
         t = self.torch
         xS, xT = self._xyz(xyzS), self._xyz(xyzT)
         T = np.zeros(16, np.float32)
@@ -668,11 +670,14 @@ class Context:
         st = IcpStats()
         head = (self.h, _ptr(xS), C.c_int64(xS.shape[0]), xS.shape[1], _ptr(xT), C.c_int64(xT.shape[0]), xT.shape[1], C.byref(params))
         tail = (T.ctypes.data_as(C.POINTER(C.c_float)), _ptr(out), C.byref(st))
-        if guess is None:
+        g = None if guess is None else np.ascontiguousarray(guess, dtype=np.float32).reshape(16)
+        gp = None if g is None else g.ctypes.data_as(C.POINTER(C.c_float))
+        if trim_ratio is not None:
+            self._check(self.lib.ghicp_gicp_trimmed_from(*head, gp, C.c_float(trim_ratio), *tail))
+        elif guess is None:
             self._check(self.lib.ghicp_gicp(*head, *tail))
         else:
-            g = np.ascontiguousarray(guess, dtype=np.float32).reshape(16)
-            self._check(self.lib.ghicp_gicp_from(*head, g.ctypes.data_as(C.POINTER(C.c_float)), *tail))
+            self._check(self.lib.ghicp_gicp_from(*head, gp, *tail))
         d = {k: getattr(st, k) for k, _ in IcpStats._fields_ if k != "pad_"}
         d.update(T=T.reshape(4, 4), transformed=out)
         return d
@@ -907,11 +912,12 @@ def _refine_clouds_reciprocal(self, params, pairs, inits=None, max_concurrent=0)
     return _refine_clouds(self, params, pairs, inits, max_concurrent, _entry="ghicp_refine_clouds_reciprocal")
 
 
-def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
+def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0, trim_ratio=None):
     """ghicp_gicp_clouds: generalized ICP of the down-sampled clouds of every (Cloud S, Cloud T) from Rt_init (n x 4 x 4 f64; None: identity)
     in one launch sequence per outer iteration.  Both clouds of every pair must have been through Cloud.prepare_gicp with the parameters'
     (covariance_k, gicp_epsilon).  Returns per pair the dict of Context.gicp (without the transformed cloud): T is the total source->target
-    pose, Rt_refined the same as f64."""
+    pose, Rt_refined the same as f64.  trim_ratio: None, or the share of the correspondences every outer iteration keeps
+    (ghicp_gicp_clouds_trimmed: in (0, 1], or 0 for each pair's own overlap estimate from the gate, which needs params.use_trimmed)."""
     n = len(pairs)
     if n == 0:
         return []
@@ -921,8 +927,11 @@ def _gicp_clouds(self, params, pairs, Rt_init=None, max_concurrent=0):
     if Rt_init is not None:
         init = np.ascontiguousarray(Rt_init, dtype=np.float64).reshape(n, 16)
     res = (GicpResult * n)()
-    self._check(self.lib.ghicp_gicp_clouds(self.h, C.byref(params), n, HS, HT, init.ctypes.data_as(C.c_void_p) if init is not None else None,
-                                           int(max_concurrent), res))
+    ip = init.ctypes.data_as(C.c_void_p) if init is not None else None
+    if trim_ratio is None:
+        self._check(self.lib.ghicp_gicp_clouds(self.h, C.byref(params), n, HS, HT, ip, int(max_concurrent), res))
+    else:
+        self._check(self.lib.ghicp_gicp_clouds_trimmed(self.h, C.byref(params), n, HS, HT, ip, C.c_float(trim_ratio), int(max_concurrent), res))
     out = []
     for r in res:
         d = {k: getattr(r.stats, k) for k, _ in IcpStats._fields_ if k != "pad_"}

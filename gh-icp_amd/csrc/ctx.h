@@ -93,6 +93,8 @@ enum BufSlot {
   // (all of them; those of a k-NN pass), the k-NN pass's normals and covariances before they go to the handles (the sorts and cell tables
   // of a chunk reuse the B_GRID_* / B_GRID2_* slots, the neighbour lists the B_FE_SORTK / B_FE_SORTK2 / B_FE_COUNT slots of the single-cloud calls)
   B_PP_DESC, B_PP_BOX, B_PP_CAT, B_PP_CATK, B_PP_NRM, B_PP_COV,
+  // trimmed generalized ICP (icp.hip, refine_gicp.hip): the select records, one per pair (the histograms reuse B_ICP_KEYS of the ICP loop)
+  B_GICP_SEL,
   B_NUM
 };
 
@@ -105,9 +107,10 @@ enum KtSlot { KT_PCA = 0, KT_BSC, KT_KM_SOLVE, KT_CD_ROWMIN, KT_KM_WEIGHTS, KT_F
               KT_GICP_CLOUDS,                                                // one chunk of the batched generalized ICP (refine_gicp.hip): upload -> final states
               KT_REFINE_GRID,                                                // inside KT_REFINE: one iteration's source grids of the reciprocal test (refine_recip.hip): boxes -> cell table
               KT_PP_GRIDS, KT_PP_KNN,                                        // one chunk of the batched prepare (prepare_clouds.hip): the grids that go into the handles; the k-NN passes (grid, search, normals / covariances)
+              KT_GICP_SELECT,                                                // inside a trimmed generalized ICP (icp.hip; refine_gicp.hip, there inside its KT_GICP_CLOUDS): one outer iteration's radix select, histogram reset -> threshold
               KT_NUM };
 static const char* const kKtNames[KT_NUM] = {"pca_cells", "bsc", "km_solve", "cd_rowmin", "km_weights", "fd_bsc", "nms_round", "voxel_sort",
-                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds", "refine_recip_grid", "prepare_grids", "prepare_knn"};
+                                             "fb_voxel", "fb_grid", "fb_prune", "fb_rank", "fb_out", "pair_loop", "transform", "pair_loop_dispatch", "refine", "gicp_clouds", "refine_recip_grid", "prepare_grids", "prepare_knn", "gicp_select"};
 
 struct ghicp_ctx {
   // optional per-kernel timing

@@ -212,6 +212,28 @@ __global__ __launch_bounds__(64) void k_gicp_solve(GicpState* st, const double* 
 
 __global__ void k_gicp_outer(GicpState* st) { gicp_outer_body(st); }
 
+// The trimmed loop (ghicp_gicp_trimmed_from): between the search and k_gicp_prep, k_gicp_reject, k_gicp_trim_prep, the radix select of the ICP
+// path over the survivors (the bodies of k_sel_pass / k_sel_final on the GicpSel record) and k_gicp_mahal_trim in the place of k_gicp_mahal.
+__global__ __launch_bounds__(256) void k_gicp_reject(int* __restrict__ nn, const float* __restrict__ nd, int ns, const GicpState* __restrict__ st,
+                                                     GicpSel* __restrict__ sel) {
+  gicp_reject_body(nn, nd, ns, blockIdx.x * 256 + threadIdx.x, st, sel);
+}
+
+__global__ void k_gicp_trim_prep(const GicpState* __restrict__ st, GicpSel* __restrict__ sel) { gicp_trim_prep_body(st, sel); }
+
+__global__ __launch_bounds__(256) void k_gicp_sel_pass(int pass, const int* __restrict__ nn, const float* __restrict__ nd, int n, GicpSel* __restrict__ sel,
+                                                       unsigned* __restrict__ hist) {
+  sel_pass_body(pass, nn, nd, n, sel, hist, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void k_gicp_sel_final(GicpSel* __restrict__ sel, const unsigned* __restrict__ hist) { sel_final_body(sel, hist); }
+
+__global__ __launch_bounds__(256) void k_gicp_mahal_trim(int* __restrict__ nn, const float* __restrict__ nd, int ns, const double* __restrict__ covS,
+                                                         const double* __restrict__ covT, const GicpState* __restrict__ st,
+                                                         const GicpSel* __restrict__ sel, double* __restrict__ mahal, double* __restrict__ part) {
+  gicp_mahal_trim_body(nn, nd, ns, covS, covT, st, sel, mahal, part, blockIdx.x);
+}
+
 }  // namespace
 
 int gh_icp_build_index(ghicp_ctx* ctx, const float* xyz, long long n, int stride, icpdev::NnIndex* out) {
@@ -467,21 +489,34 @@ extern "C" int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int str
   return ghicp_gicp_from(ctx, xyzS, ns, strideS, xyzT, nt, strideT, P, nullptr, T16, transformed, stats);
 }
 
+#define GICP_ARG(cond)                                                                 \
+  do {                                                                                 \
+    if (!(cond)) return ctx->fail(GHICP_ERR_ARG, "%s: bad argument (%s)", who, #cond); \
+  } while (0)
+
+// The body of ghicp_gicp_from and ghicp_gicp_trimmed_from (`who` names the one that was called).
 // gicp_reg with transformation_ starting at guess16 (NULL: the identity, which is ghicp_gicp).  The source points and their covariances stay
 // in the source's own frame: k_gicp_apply moves the points by transformation_, k_gicp_mahal rotates C_S by its R, k_gicp_prep takes x from it.
-extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
-                               const ghicp_gicp_params* P, const float* guess16, float* T16, float* transformed, ghicp_icp_stats* stats) {
-  GH_ENTER(ctx);
-  GH_ARG(P != nullptr && T16 != nullptr && stats != nullptr && ns >= 0 && nt >= 0 && ns < (1ll << 31) - 2 && nt < (1ll << 31) - 2 && strideS >= 3 &&
-         strideT >= 3);
-  GH_ARG(P->covariance_k >= 1 && P->covariance_k <= 20 && P->max_inner_iter >= 1 && P->max_inner_iter <= 100);
-  GH_ARG(P->max_correspondence_distance > 0.0 && P->gicp_epsilon > 0.0 && P->transformation_epsilon > 0.0 && P->rotation_epsilon > 0.0);
-  if (P->use_trimmed) GH_ARG(P->thre_dis > 0.f);
+// trim: every outer iteration keeps the floor(ratio * count) correspondences with the smallest (d^2, index) of the count within the distance
+// (trim_ratio in (0, 1], or 0 for the overlap the gate estimated); without it trim_ratio is not read and use_trimmed is the gate alone.
+static int gicp_from_impl(ghicp_ctx* ctx, const char* who, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                          const ghicp_gicp_params* P, const float* guess16, bool trim, float trim_ratio, float* T16, float* transformed,
+                          ghicp_icp_stats* stats) {
+  GICP_ARG(P != nullptr && T16 != nullptr && stats != nullptr && ns >= 0 && nt >= 0 && ns < (1ll << 31) - 2 && nt < (1ll << 31) - 2 && strideS >= 3 &&
+           strideT >= 3);
+  GICP_ARG(P->covariance_k >= 1 && P->covariance_k <= 20 && P->max_inner_iter >= 1 && P->max_inner_iter <= 100);
+  GICP_ARG(P->max_correspondence_distance > 0.0 && P->gicp_epsilon > 0.0 && P->transformation_epsilon > 0.0 && P->rotation_epsilon > 0.0);
+  if (P->use_trimmed) GICP_ARG(P->thre_dis > 0.f);
+  if (trim) {
+    GICP_ARG(std::isfinite(trim_ratio) && trim_ratio >= 0.f && trim_ratio <= 1.f);
+    if (trim_ratio == 0.f && !P->use_trimmed)
+      return ctx->fail(GHICP_ERR_ARG, "%s: trim_ratio = 0 asks for the overlap estimate of the gate, which needs use_trimmed = 1", who);
+  }
   const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   float T0[16];
   memcpy(T0, guess16 ? guess16 : I16, sizeof(T0));
-  for (int e = 0; e < 16; e++) GH_ARG(std::isfinite(T0[e]));
-  GH_ARG(T0[12] == 0.f && T0[13] == 0.f && T0[14] == 0.f && T0[15] == 1.f);
+  for (int e = 0; e < 16; e++) GICP_ARG(std::isfinite(T0[e]));
+  GICP_ARG(T0[12] == 0.f && T0[13] == 0.f && T0[14] == 0.f && T0[15] == 1.f);
   hipStream_t s = ctx->stream;
   memset(stats, 0, sizeof(*stats));
   Stager sg(ctx);
@@ -491,8 +526,8 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
   GH_TRY(sg.in_cloud(xyzT, (size_t)nt * strideT, &dT));
   GH_TRY(sg.out(transformed, (size_t)ns * 3, &dOut));
 
-  if (P->use_trimmed) {  // common_reg.cpp:240-246: the only effect of the trimmed flag on GICP (the rejector is never consulted)
-    float ratio = 0.f;
+  float ratio = trim_ratio;
+  if (P->use_trimmed) {  // common_reg.cpp:240-246: the only effect of the trimmed flag on gicp_reg (the rejector is never consulted)
     if (guess16 && ns > 0) {  // the gate sees the source where the guess puts it (the float expression of k_gicp_apply)
       float4* moved;
       GH_TRY(ctx->reserve(B_ICP_CUR, (size_t)ns + 1, &moved));
@@ -505,6 +540,7 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
     }
     stats->overlap = ratio;
     if (ratio < P->min_overlap) { sg.outs.clear(); return GHICP_OK; }  // "This registration would not be done"
+    if (trim_ratio != 0.f) ratio = trim_ratio;  // (0: the estimate feeds the rejector, as in icp_reg)
   }
   stats->done = 1;
   if (ns == 0 || nt == 0) {
@@ -524,7 +560,8 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
   float* nd;
   double *covS, *covT, *mahal, *part;
   GicpState* st;
-  unsigned* pend;
+  GicpSel* sel = nullptr;
+  unsigned *pend, *hist = nullptr;
   GH_TRY(ctx->reserve(B_GICP_COVS, (size_t)ns * 6 + 6, &covS));
   GH_TRY(ctx->reserve(B_GICP_COVT, (size_t)nt * 6 + 6, &covT));
   GH_TRY(gh_gicp_cov_dev(ctx, dS, ns, strideS, P->covariance_k, P->gicp_epsilon, covS));
@@ -537,6 +574,11 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
   GH_TRY(ctx->reserve(B_ICP_ND, (size_t)ns + 1, &nd));
   GH_TRY(ctx->reserve(B_ICP_PART, (size_t)NBLK * NPART, &part));
   GH_TRY(ctx->reserve(B_ICP_STATE, 1, &st));
+  if (trim) {
+    GH_TRY(ctx->reserve(B_ICP_KEYS, (size_t)6 * SEL_BINS, &hist));
+    GH_TRY(ctx->reserve(B_GICP_SEL, 1, &sel));
+    GH_HIP(hipMemsetAsync(sel, 0, sizeof(GicpSel), s));
+  }
   hipLaunchKernelGGL(k_pack4, dim3(cdiv(ns, 256)), dim3(256), 0, s, dS, (long long)ns, strideS, src4);
   hipLaunchKernelGGL(k_pack4, dim3(cdiv(nt, 256)), dim3(256), 0, s, dT, (long long)nt, strideT, tgt4);
   NnIndex XT;
@@ -550,14 +592,27 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
   hst.inv_eps_r = 1.0 / P->rotation_epsilon;
   hst.inv_eps_t = 1.0 / P->transformation_epsilon;
   hst.max_iter = P->max_iter;
+  hst.ratio = trim ? ratio : 0.f;
   GH_HIP(hipMemcpyAsync(st, &hst, sizeof(hst), hipMemcpyHostToDevice, s));
   GicpState* pin = reinterpret_cast<GicpState*>(ctx->pinned);
   static_assert(sizeof(GicpState) <= 4096, "status record must fit the pinned scratch");
   const int gS = cdiv(ns, 256);
+  const int gSel = min(cdiv(ns, 2048), 512);
   for (;;) {
     hipLaunchKernelGGL(k_gicp_apply, dim3(gS), dim3(256), 0, s, src4, (int)ns, st, cur);
     GH_TRY(nn_search(ctx, XT, cur, (int)ns, nn, nd));
-    hipLaunchKernelGGL(k_gicp_mahal, dim3(NBLK), dim3(256), 0, s, nn, nd, (int)ns, covS, covT, st, mahal, part);
+    if (trim) {
+      hipLaunchKernelGGL(k_gicp_reject, dim3(gS), dim3(256), 0, s, nn, nd, (int)ns, st, sel);
+      hipLaunchKernelGGL(k_gicp_trim_prep, dim3(1), dim3(1), 0, s, st, sel);
+      hipEvent_t kt = ctx->kt_begin(KT_GICP_SELECT);
+      GH_HIP(hipMemsetAsync(hist, 0, (size_t)6 * SEL_BINS * sizeof(unsigned), s));
+      for (int pass = 0; pass < 6; pass++) hipLaunchKernelGGL(k_gicp_sel_pass, dim3(gSel), dim3(256), 0, s, pass, nn, nd, (int)ns, sel, hist);
+      hipLaunchKernelGGL(k_gicp_sel_final, dim3(1), dim3(256), 0, s, sel, hist);
+      ctx->kt_end(KT_GICP_SELECT, kt);
+      hipLaunchKernelGGL(k_gicp_mahal_trim, dim3(NBLK), dim3(256), 0, s, nn, nd, (int)ns, covS, covT, st, sel, mahal, part);
+    } else {
+      hipLaunchKernelGGL(k_gicp_mahal, dim3(NBLK), dim3(256), 0, s, nn, nd, (int)ns, covS, covT, st, mahal, part);
+    }
     hipLaunchKernelGGL(k_gicp_prep, dim3(1), dim3(64), 0, s, st, part);
     for (int k = 0; k < P->max_inner_iter; k++) {
       hipLaunchKernelGGL(k_gicp_acc, dim3(NBLK), dim3(256), 0, s, src4, tgt4, nn, (int)ns, mahal, st, part);
@@ -589,4 +644,17 @@ extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, in
   for (int b = 0; b < NBLK; b++) f += hp[b];
   stats->fitness = f / (double)ns;
   return sg.finish();
+}
+
+extern "C" int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                               const ghicp_gicp_params* P, const float* guess16, float* T16, float* transformed, ghicp_icp_stats* stats) {
+  GH_ENTER(ctx);
+  return gicp_from_impl(ctx, "ghicp_gicp_from", xyzS, ns, strideS, xyzT, nt, strideT, P, guess16, false, 1.0f, T16, transformed, stats);
+}
+
+extern "C" int ghicp_gicp_trimmed_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                                       const ghicp_gicp_params* P, const float* guess16, float trim_ratio, float* T16, float* transformed,
+                                       ghicp_icp_stats* stats) {
+  GH_ENTER(ctx);
+  return gicp_from_impl(ctx, "ghicp_gicp_trimmed_from", xyzS, ns, strideS, xyzT, nt, strideT, P, guess16, true, trim_ratio, T16, transformed, stats);
 }

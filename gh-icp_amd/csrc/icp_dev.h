@@ -268,8 +268,10 @@ __device__ inline bool overlap_hit(const NnGrid& G, float px, float py, float pz
   return hit;
 }
 
-// CorrespondenceRejectorTrimmed::getRemainingCorrespondences: floor(overlap_ratio * float(size))
-__device__ inline void icp_prep_body(IcpState* st) {
+// CorrespondenceRejectorTrimmed::getRemainingCorrespondences: floor(overlap_ratio * float(size)).  State: IcpState, or the select record of
+// the trimmed generalized ICP (GicpSel below) -- one rule, one select for both loops
+template <typename State>
+__device__ inline void icp_prep_body(State* st) {
   unsigned nv = st->count;
   if (st->trimmed) {
     const unsigned t = (unsigned)(int)floorf(st->ratio * (float)st->count);
@@ -311,7 +313,8 @@ __device__ inline unsigned sel_pick(const unsigned* __restrict__ hist, unsigned 
   return pick_s[0];
 }
 
-__device__ inline void sel_pass_body(int pass, const int* __restrict__ nn, const float* __restrict__ nd, int n, IcpState* __restrict__ st,
+template <typename State>
+__device__ inline void sel_pass_body(int pass, const int* __restrict__ nn, const float* __restrict__ nd, int n, State* __restrict__ st,
                                      unsigned* __restrict__ hist, unsigned blk, unsigned nblk) {
   if (st->sel_done || (pass > 3 && st->istar == 0)) return;
   __shared__ unsigned lh[SEL_BINS];
@@ -352,7 +355,8 @@ __device__ inline void sel_pass_body(int pass, const int* __restrict__ nn, const
     if (lh[k]) atomicAdd(&out[k], lh[k]);
 }
 
-__device__ inline void sel_final_body(IcpState* __restrict__ st, const unsigned* __restrict__ hist) {
+template <typename State>
+__device__ inline void sel_final_body(State* __restrict__ st, const unsigned* __restrict__ hist) {
   if (st->sel_done) return;
   __shared__ int scan_s[20];
   __shared__ unsigned pick_s[2];
@@ -370,8 +374,10 @@ struct CorrView {
   int ns;
 };
 
-// source point e -> its target j if the correspondence survives the rejectors, else -1
-__device__ inline int corr_at(const CorrView& V, const IcpState* __restrict__ st, unsigned e, int* j) {
+// source point e -> its target j if the correspondence survives the rejectors, else -1: its key (d2 bits, source index) lies below the
+// threshold K* of the select (nothing to trim: K* is the largest key).  State: IcpState, or the trimmed generalized ICP's GicpSel
+template <typename State>
+__device__ inline int corr_at(const CorrView& V, const State* __restrict__ st, unsigned e, int* j) {
   *j = V.nn[e];
   if (*j < 0) return -1;
   const unsigned db = __float_as_uint(V.nd[e]);
@@ -576,8 +582,22 @@ struct GicpState {
   unsigned count;                // correspondences of this iteration
   int iterations, max_iter, converged, reason, inner_done, inner_steps, pad_;
   // batched loop (refine_gicp.hip) only: a pair the overlap gate refused (or an empty one) never runs; the sum behind getFitnessScore()
-  int refused, pad2_;
+  int refused;
+  float ratio;                   // trimmed loop only: the share of the correspondences within the distance that is kept, fixed for the registration
   double fit_sum;
+};
+
+// The trimmed loop (ghicp_gicp_trimmed_from, ghicp_gicp_clouds_trimmed) keeps a select record beside its GicpState: the fields of an
+// IcpState that icp_prep_body, sel_pass_body, sel_final_body and corr_at read and write, so the ICP path's rule and radix select serve it
+// as they are.  `acc` gathers the survivors of the distance rejection (one integer atomic per block) until the prep step takes it.
+struct GicpSel {
+  unsigned count, nv;  // within the distance / kept after trimming
+  int trimmed;         // 1: the rule of icp_prep_body applies (a ratio of 1 keeps everything)
+  float ratio;
+  unsigned sel_prefix[6], sel_rank[6];
+  unsigned d2star, istar;
+  int sel_done;
+  unsigned acc;
 };
 
 constexpr double kGicpStop = 1e-10;  // N8: the inner loop stops once max |dx| < this
@@ -615,8 +635,27 @@ __device__ inline void gicp_apply_body(const float4* __restrict__ src, int n, in
                        ((M[8] * P.x + M[9] * P.y) + M[10] * P.z) + M[11], 0.f);
 }
 
-// M_i = (R C_S,i R^T + C_T,j)^-1 (symmetric: upper triangle of R C R^T + C_T, inverse by cofactors) for every correspondence with
-// d^2 < max distance^2; rejected points get nn = -1.  Block partials: [0] accepted count, [1] sum of their d^2.
+// M_i = (R C_S,i R^T + C_T,j)^-1 (symmetric: upper triangle of R C R^T + C_T, inverse by cofactors), 6 entries
+__device__ inline void gicp_mahal_at(const double* R, const double* cs, const double* ct, double* __restrict__ mahal, unsigned i) {
+  const double C[9] = {cs[0], cs[1], cs[2], cs[1], cs[3], cs[4], cs[2], cs[4], cs[5]};
+  double P[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) P[r * 3 + c] = (R[r * 3] * C[c] + R[r * 3 + 1] * C[3 + c]) + R[r * 3 + 2] * C[6 + c];
+  const int rr[6] = {0, 0, 0, 1, 1, 2}, cc[6] = {0, 1, 2, 1, 2, 2};
+  double A[6];
+  for (int e = 0; e < 6; e++) {
+    const int r = rr[e], c = cc[e];
+    A[e] = ((P[r * 3] * R[c * 3] + P[r * 3 + 1] * R[c * 3 + 1]) + P[r * 3 + 2] * R[c * 3 + 2]) + ct[e];
+  }
+  const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5];
+  const double k00 = d * f - e * e, k01 = c * e - b * f, k02 = b * e - c * d, k11 = a * f - c * c, k12 = b * c - a * e, k22 = a * d - b * b;
+  const double det = (a * k00 + b * k01) + c * k02;
+  double* M = &mahal[(size_t)i * 6];
+  M[0] = k00 / det; M[1] = k01 / det; M[2] = k02 / det; M[3] = k11 / det; M[4] = k12 / det; M[5] = k22 / det;
+}
+
+// M_i for every correspondence with d^2 < max distance^2; rejected points get nn = -1.  Block partials: [0] accepted count, [1] sum of
+// their d^2.
 __device__ inline void gicp_mahal_body(int* __restrict__ nn, const float* __restrict__ nd, int ns, const double* __restrict__ covS,
                                        const double* __restrict__ covT, const GicpState* __restrict__ st, double* __restrict__ mahal,
                                        double* __restrict__ part, unsigned blk) {
@@ -629,23 +668,53 @@ __device__ inline void gicp_mahal_body(int* __restrict__ nn, const float* __rest
     const int j = nn[i];
     if (j < 0) continue;
     if (!((double)nd[i] < maxd2)) { nn[i] = -1; continue; }
-    const double* cs = &covS[(size_t)i * 6];
-    const double* ct = &covT[(size_t)j * 6];
-    const double C[9] = {cs[0], cs[1], cs[2], cs[1], cs[3], cs[4], cs[2], cs[4], cs[5]};
-    double P[9];
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) P[r * 3 + c] = (R[r * 3] * C[c] + R[r * 3 + 1] * C[3 + c]) + R[r * 3 + 2] * C[6 + c];
-    const int rr[6] = {0, 0, 0, 1, 1, 2}, cc[6] = {0, 1, 2, 1, 2, 2};
-    double A[6];
-    for (int e = 0; e < 6; e++) {
-      const int r = rr[e], c = cc[e];
-      A[e] = ((P[r * 3] * R[c * 3] + P[r * 3 + 1] * R[c * 3 + 1]) + P[r * 3 + 2] * R[c * 3 + 2]) + ct[e];
+    gicp_mahal_at(R, &covS[(size_t)i * 6], &covT[(size_t)j * 6], mahal, i);
+    acc[0] += 1.0;
+    acc[1] += (double)nd[i];
+  }
+  store_partials(acc, 2, red, part, blk);
+}
+
+// ---- the trimmed loop: the rejector PCL's GICP never consults, applied.  Per outer iteration, after the search: the distance rejection with
+// its count (gicp_reject_body), the rule of the ICP path (gicp_trim_prep_body -> icp_prep_body), its radix select over the survivors
+// (sel_pass_body / sel_final_body on the GicpSel), then M_i, the count and the MSE over the kept set only (gicp_mahal_trim_body).  The rest of
+// the iteration is the untrimmed loop's: gicp_prep_body sees the kept count, fewer than 4 ends the loop.
+// Per point: a correspondence with d^2 >= max distance^2 gets nn = -1; the survivors are counted.  Every thread of the block calls this.
+__device__ inline void gicp_reject_body(int* __restrict__ nn, const float* __restrict__ nd, int ns, int i, const GicpState* __restrict__ st,
+                                        GicpSel* __restrict__ sel) {
+  bool keep = false;
+  if (i < ns && nn[i] >= 0) {
+    keep = (double)nd[i] < st->maxd2;
+    if (!keep) nn[i] = -1;
+  }
+  block_count_add(keep, &sel->acc);
+}
+
+// one thread: count = the survivors, nv = min(count, floor(ratio * float(count))), the select's start
+__device__ inline void gicp_trim_prep_body(const GicpState* __restrict__ st, GicpSel* __restrict__ sel) {
+  sel->count = sel->acc;
+  sel->acc = 0;
+  sel->trimmed = 1;
+  sel->ratio = st->ratio;
+  icp_prep_body(sel);
+}
+
+// gicp_mahal_body for the kept correspondences (key below K*); the trimmed ones get nn = -1.  Block partials as there, over the kept set.
+__device__ inline void gicp_mahal_trim_body(int* __restrict__ nn, const float* __restrict__ nd, int ns, const double* __restrict__ covS,
+                                            const double* __restrict__ covT, const GicpState* __restrict__ st, const GicpSel* __restrict__ sel,
+                                            double* __restrict__ mahal, double* __restrict__ part, unsigned blk) {
+  __shared__ double red[16];
+  double R[9];
+  for (int e = 0; e < 9; e++) R[e] = (double)st->T[(e / 3) * 4 + e % 3];
+  double acc[2] = {0, 0};
+  const CorrView V = {nn, nd, nullptr, nullptr, ns};
+  for (unsigned i = blk * 256u + threadIdx.x; i < (unsigned)ns; i += NBLK * 256u) {
+    int j;
+    if (corr_at(V, sel, i, &j) < 0) {
+      if (j >= 0) nn[i] = -1;
+      continue;
     }
-    const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5];
-    const double k00 = d * f - e * e, k01 = c * e - b * f, k02 = b * e - c * d, k11 = a * f - c * c, k12 = b * c - a * e, k22 = a * d - b * b;
-    const double det = (a * k00 + b * k01) + c * k02;
-    double* M = &mahal[(size_t)i * 6];
-    M[0] = k00 / det; M[1] = k01 / det; M[2] = k02 / det; M[3] = k11 / det; M[4] = k12 / det; M[5] = k22 / det;
+    gicp_mahal_at(R, &covS[(size_t)i * 6], &covT[(size_t)j * 6], mahal, i);
     acc[0] += 1.0;
     acc[1] += (double)nd[i];
   }

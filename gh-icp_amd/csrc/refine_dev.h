@@ -48,6 +48,10 @@ struct RefineArgs : ChunkArrays<RefinePair, icpdev::IcpState> {
 struct GicpArgs : ChunkArrays<GicpPair, icpdev::GicpState> {
   double* mahal;  // 6 per source point
 };
+struct GicpTrimArgs : GicpArgs {  // the trimmed loop: the kernels it shares with the untrimmed one take the GicpArgs part
+  icpdev::GicpSel* sel;  // one select record per pair
+  unsigned* hist;        // 6 x SEL_BINS per pair
+};
 
 constexpr int COARSE_BLK = 512;  // blocks per pair of the coarse search (any count gives the same result: one wave per query)
 

@@ -14,6 +14,13 @@
 // What this loop shares with the batched ICP lives in one place: the descriptors, the prologue of the 2-D launches and the kernels
 // k_chunk_* (search, overlap count, fitness sum) in refine_dev.h, the chunk in flight (RfChunk) in refine_run.h.  Below: this method's
 // kernels, its iteration, its results (GicpMethod), its argument checks.
+//   ghicp_gicp_clouds_trimmed the loop of ghicp_gicp_trimmed_from in the same shape (GicpMethod<true>): between the search and k_gb_prep the
+//                             distance rejection with its count (k_gb_reject), the rule and the radix select of the batched ICP over the survivors
+//                             (k_gb_trim_prep, k_gb_sel_pass, k_gb_sel_final: the bodies of refine.hip's on the pair's GicpSel record, 6 x SEL_BINS
+//                             histogram words per pair) and k_gb_mahal_trim in the place of k_gb_mahal.  A pair that keeps every survivor returns
+//                             from the select passes at once.  The integer counters are those of the single-pair kernels; no further host wait.
+#include <type_traits>
+
 #include "refine_run.h"
 
 namespace {
@@ -68,14 +75,55 @@ __global__ __launch_bounds__(64) void k_gb_outer(GicpArgs A, int np) {
   A.flag[p] = frozen(st) ? 1 : 0;
 }
 
-// What RfChunk (refine_run.h) asks of a method: the loop of ghicp_gicp_from
+// ---- the trimmed loop's own kernels
+__device__ inline unsigned* hist_of(const GicpTrimArgs& A, unsigned p) { return A.hist + (size_t)p * 6 * SEL_BINS; }
+
+__global__ __launch_bounds__(256) void k_gb_reject(GicpTrimArgs A) {
+  const GicpPair& D = A.pair[blockIdx.y];
+  if (!point_block(D.ns, &A.st[blockIdx.y])) return;
+  gicp_reject_body(A.nn + D.off, A.nd + D.off, D.ns, blockIdx.x * 256 + threadIdx.x, &A.st[blockIdx.y], &A.sel[blockIdx.y]);
+}
+
+__global__ __launch_bounds__(64) void k_gb_trim_prep(GicpTrimArgs A, int np) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= np || frozen(&A.st[p])) return;
+  gicp_trim_prep_body(&A.st[p], &A.sel[p]);
+}
+
+// min(cdiv(ns, 2048), 512) blocks per pair, as in the single-pair launch
+__global__ __launch_bounds__(256) void k_gb_sel_pass(GicpTrimArgs A, int pass) {
+  const unsigned p = blockIdx.y;
+  const GicpPair& D = A.pair[p];
+  const unsigned nblk = (unsigned)min(cdiv_dev(D.ns, 2048), 512);
+  if (blockIdx.x >= nblk) return;
+  if (frozen(&A.st[p])) return;
+  sel_pass_body(pass, A.nn + D.off, A.nd + D.off, D.ns, &A.sel[p], hist_of(A, p), blockIdx.x, nblk);
+}
+
+__global__ __launch_bounds__(256) void k_gb_sel_final(GicpTrimArgs A) {
+  const unsigned p = blockIdx.x;
+  if (frozen(&A.st[p])) return;
+  sel_final_body(&A.sel[p], hist_of(A, p));
+}
+
+__global__ __launch_bounds__(256) void k_gb_mahal_trim(GicpTrimArgs A) {
+  const unsigned p = blockIdx.y;
+  const GicpState* st = &A.st[p];
+  if (frozen(st)) return;
+  const GicpPair& D = A.pair[p];
+  gicp_mahal_trim_body(A.nn + D.off, A.nd + D.off, D.ns, D.covS, D.covT, st, &A.sel[p], A.mahal + D.off * 6, part_of(A, p), blockIdx.x);
+}
+
+// What RfChunk (refine_run.h) asks of a method: the loop of ghicp_gicp_from, or (TRIM) of ghicp_gicp_trimmed_from
+template <bool TRIM>
 struct GicpMethod {
-  typedef GicpArgs Args;
+  typedef typename std::conditional<TRIM, GicpTrimArgs, GicpArgs>::type Args;
   typedef ghicp_gicp_result Result;
   typedef ghicp_gicp_params Params;
   static constexpr int TIMER = KT_GICP_CLOUDS;
   typedef RfChunk<GicpMethod> Chunk;
   const ghicp_gicp_params* P;
+  float trim_ratio;  // TRIM: in (0, 1] for every pair, or 0: each pair's own overlap estimate from the gate
 
   void pair(const ghicp_cloud* a, const ghicp_cloud* b, GicpPair& D, GicpState& st, ghicp_gicp_result& R) const {
     memcpy(R.T, D.init, sizeof(D.init));  // a refused pair: T = the rounded init
@@ -84,25 +132,58 @@ struct GicpMethod {
     st.inv_eps_r = 1.0 / P->rotation_epsilon;
     st.inv_eps_t = 1.0 / P->transformation_epsilon;
     st.max_iter = P->max_iter;
+    st.ratio = TRIM ? trim_ratio : 0.f;
     D.covT = b->gc_cov.as<double>();
     D.covS = a->gc_cov.as<double>();
   }
 
-  int reserve(Chunk& C, ReserveAt at) const { return at == RESERVE_PER_POINT ? C.ctx->reserve(B_GICP_MAHAL, (size_t)C.npts * 6 + 6, &C.A.mahal) : GHICP_OK; }
+  int reserve(Chunk& C, ReserveAt at) const {
+    if (at == RESERVE_PER_POINT) return C.ctx->reserve(B_GICP_MAHAL, (size_t)C.npts * 6 + 6, &C.A.mahal);
+    if constexpr (TRIM) {
+      if (at == RESERVE_PER_PAIR) {  // the histograms where the batched ICP keeps its own
+        GH_TRY(C.ctx->reserve(B_ICP_KEYS, (size_t)C.np * 6 * SEL_BINS, &C.A.hist));
+        return C.ctx->reserve(B_GICP_SEL, (size_t)C.np, &C.A.sel);
+      }
+    }
+    return GHICP_OK;
+  }
 
-  void accept(GicpState&, float) const {}  // use_trimmed acts as the gate only
+  // untrimmed: use_trimmed acts as the gate only.  Trimmed with trim_ratio = 0: the pair's estimate feeds its rejector, as in icp_reg
+  void accept(GicpState& st, float ratio) const {
+    if (TRIM && trim_ratio == 0.f) st.ratio = ratio;
+  }
 
   // every search is of the source under the pair's current transformation_
   int search(Chunk& C, SearchPhase ph) const {
     const int final = ph == SEARCH_FINAL ? 1 : 0;
-    return C.nn_search(final, [&] { hipLaunchKernelGGL(k_gb_apply, dim3(C.max_gs, C.np), dim3(256), 0, C.s, C.A, final); });
+    if constexpr (TRIM) {
+      ghicp_ctx* ctx = C.ctx;
+      if (ph == SEARCH_FIRST) GH_HIP(hipMemsetAsync(C.A.sel, 0, (size_t)C.np * sizeof(GicpSel), C.s));  // nothing counted yet
+    }
+    const GicpArgs& A = C.A;
+    return C.nn_search(final, [&] { hipLaunchKernelGGL(k_gb_apply, dim3(C.max_gs, C.np), dim3(256), 0, C.s, A, final); });
   }
 
   int iteration(Chunk& C) const {
     const GicpArgs& A = C.A;
     const int np = C.np;
     hipStream_t s = C.s;
-    hipLaunchKernelGGL(k_gb_mahal, dim3(NBLK, np), dim3(256), 0, s, A);
+    // the correspondences of the iteration: their Mahalanobis matrices, their count and d^2 sum in the partial records
+    if constexpr (TRIM) {
+      const GicpTrimArgs& TA = C.A;
+      const int max_sel = min(cdiv(C.max_gs, 8), 512);  // blocks of the radix select of the largest source: min(cdiv(ns, 2048), 512)
+      ghicp_ctx* ctx = C.ctx;
+      hipLaunchKernelGGL(k_gb_reject, dim3(C.max_gs, np), dim3(256), 0, s, TA);
+      hipLaunchKernelGGL(k_gb_trim_prep, dim3(cdiv(np, 64)), dim3(64), 0, s, TA, np);
+      hipEvent_t kt = ctx->kt_begin(KT_GICP_SELECT);
+      GH_HIP(hipMemsetAsync(TA.hist, 0, (size_t)np * 6 * SEL_BINS * sizeof(unsigned), s));
+      for (int pass = 0; pass < 6; pass++) hipLaunchKernelGGL(k_gb_sel_pass, dim3(max_sel, np), dim3(256), 0, s, TA, pass);
+      hipLaunchKernelGGL(k_gb_sel_final, dim3(np), dim3(256), 0, s, TA);
+      ctx->kt_end(KT_GICP_SELECT, kt);
+      hipLaunchKernelGGL(k_gb_mahal_trim, dim3(NBLK, np), dim3(256), 0, s, TA);
+    } else {
+      hipLaunchKernelGGL(k_gb_mahal, dim3(NBLK, np), dim3(256), 0, s, A);
+    }
     hipLaunchKernelGGL(k_gb_prep, dim3(np), dim3(64), 0, s, A);
     for (int k = 0; k < P->max_inner_iter; k++) {
       hipLaunchKernelGGL(k_gb_acc, dim3(NBLK, np), dim3(256), 0, s, A);
@@ -147,34 +228,62 @@ extern "C" int ghicp_cloud_prepare_gicp(ghicp_cloud* c, int32_t covariance_k, do
   return GHICP_OK;
 }
 
-extern "C" int ghicp_gicp_clouds(ghicp_ctx* ctx, const ghicp_gicp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
-                                 const double* Rt_init, int32_t max_concurrent, ghicp_gicp_result* out) {
-  GH_ENTER(ctx);
-  GH_ARG(P != nullptr && n_pairs >= 0 && max_concurrent >= 0 && (n_pairs == 0 || (S != nullptr && T != nullptr && out != nullptr)));
-  GH_ARG(P->covariance_k >= 1 && P->covariance_k <= 20 && P->max_inner_iter >= 1 && P->max_inner_iter <= 100);
-  GH_ARG(P->max_correspondence_distance > 0.0 && P->gicp_epsilon > 0.0 && P->transformation_epsilon > 0.0 && P->rotation_epsilon > 0.0);
-  if (P->use_trimmed) GH_ARG(P->thre_dis > 0.f);
+namespace {
+
+#define GB_ARG(cond)                                                                   \
+  do {                                                                                 \
+    if (!(cond)) return ctx->fail(GHICP_ERR_ARG, "%s: bad argument (%s)", who, #cond); \
+  } while (0)
+
+// The body of both entry points (`who` names the one that was called): the argument checks, then the chunks
+template <bool TRIM>
+int gicp_clouds_impl(ghicp_ctx* ctx, const char* who, const ghicp_gicp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                     const double* Rt_init, float trim_ratio, int32_t max_concurrent, ghicp_gicp_result* out) {
+  GB_ARG(P != nullptr && n_pairs >= 0 && max_concurrent >= 0 && (n_pairs == 0 || (S != nullptr && T != nullptr && out != nullptr)));
+  GB_ARG(P->covariance_k >= 1 && P->covariance_k <= 20 && P->max_inner_iter >= 1 && P->max_inner_iter <= 100);
+  GB_ARG(P->max_correspondence_distance > 0.0 && P->gicp_epsilon > 0.0 && P->transformation_epsilon > 0.0 && P->rotation_epsilon > 0.0);
+  if (P->use_trimmed) GB_ARG(P->thre_dis > 0.f);
+  if (TRIM) {
+    GB_ARG(std::isfinite(trim_ratio) && trim_ratio >= 0.f && trim_ratio <= 1.f);
+    if (trim_ratio == 0.f && !P->use_trimmed)
+      return ctx->fail(GHICP_ERR_ARG, "%s: trim_ratio = 0 asks for the overlap estimate of the gate, which needs use_trimmed = 1", who);
+  }
   // every pair is checked before anything is written or launched
   std::vector<int64_t> ns_all((size_t)n_pairs);
   for (int i = 0; i < n_pairs; i++) {
     const ghicp_cloud *a = S[i], *b = T[i];
-    GH_ARG(a != nullptr && b != nullptr && a->ctx && b->ctx && a->ctx->device == ctx->device && b->ctx->device == ctx->device);
-    if (!a->ds.p || !b->ds.p) return ctx->fail(GHICP_ERR_ARG, "ghicp_gicp_clouds: a cloud of pair %d was rebuilt from stored features and holds no points", i);
-    if (!holds_cov(a, P)) return ctx->fail(GHICP_ERR_ARG, "ghicp_gicp_clouds: the source of pair %d holds no covariances for k = %d, epsilon = %g (ghicp_cloud_prepare_gicp)", i, P->covariance_k, P->gicp_epsilon);
-    if (!holds_cov(b, P)) return ctx->fail(GHICP_ERR_ARG, "ghicp_gicp_clouds: the target of pair %d holds no covariances for k = %d, epsilon = %g (ghicp_cloud_prepare_gicp)", i, P->covariance_k, P->gicp_epsilon);
-    if (!b->rf_ready) return ctx->fail(GHICP_ERR_ARG, "ghicp_gicp_clouds: the target of pair %d holds no search grids (ghicp_cloud_prepare_gicp)", i);
+    GB_ARG(a != nullptr && b != nullptr && a->ctx && b->ctx && a->ctx->device == ctx->device && b->ctx->device == ctx->device);
+    if (!a->ds.p || !b->ds.p) return ctx->fail(GHICP_ERR_ARG, "%s: a cloud of pair %d was rebuilt from stored features and holds no points", who, i);
+    if (!holds_cov(a, P)) return ctx->fail(GHICP_ERR_ARG, "%s: the source of pair %d holds no covariances for k = %d, epsilon = %g (ghicp_cloud_prepare_gicp)", who, i, P->covariance_k, P->gicp_epsilon);
+    if (!holds_cov(b, P)) return ctx->fail(GHICP_ERR_ARG, "%s: the target of pair %d holds no covariances for k = %d, epsilon = %g (ghicp_cloud_prepare_gicp)", who, i, P->covariance_k, P->gicp_epsilon);
+    if (!b->rf_ready) return ctx->fail(GHICP_ERR_ARG, "%s: the target of pair %d holds no search grids (ghicp_cloud_prepare_gicp)", who, i);
     if (Rt_init) {
       const double* M = Rt_init + (size_t)i * 16;
       bool ok = true;
       for (int e = 0; e < 16; e++) ok = ok && std::isfinite((float)M[e]);
       if (!(ok && (float)M[12] == 0.f && (float)M[13] == 0.f && (float)M[14] == 0.f && (float)M[15] == 1.f))
-        return ctx->fail(GHICP_ERR_ARG, "ghicp_gicp_clouds: Rt_init of pair %d has a non-finite entry or a last row other than (0, 0, 0, 1)", i);
+        return ctx->fail(GHICP_ERR_ARG, "%s: Rt_init of pair %d has a non-finite entry or a last row other than (0, 0, 0, 1)", who, i);
     }
     ns_all[i] = a->m;
   }
   if (n_pairs == 0) return GHICP_OK;
   size_t budget;
   GH_TRY(refine_budget(ctx, &budget));
-  GicpMethod M = {P};
-  return GicpMethod::Chunk(ctx, M, P, S, T, Rt_init, out).run(gh_gicp_plan(n_pairs, ns_all.data(), max_concurrent, budget));
+  GicpMethod<TRIM> M = {P, trim_ratio};
+  const std::vector<int> bounds = TRIM ? gh_gicp_trim_plan(n_pairs, ns_all.data(), max_concurrent, budget) : gh_gicp_plan(n_pairs, ns_all.data(), max_concurrent, budget);
+  return typename GicpMethod<TRIM>::Chunk(ctx, M, P, S, T, Rt_init, out).run(bounds);
+}
+
+}  // namespace
+
+extern "C" int ghicp_gicp_clouds(ghicp_ctx* ctx, const ghicp_gicp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                                 const double* Rt_init, int32_t max_concurrent, ghicp_gicp_result* out) {
+  GH_ENTER(ctx);
+  return gicp_clouds_impl<false>(ctx, "ghicp_gicp_clouds", P, n_pairs, S, T, Rt_init, 0.f, max_concurrent, out);
+}
+
+extern "C" int ghicp_gicp_clouds_trimmed(ghicp_ctx* ctx, const ghicp_gicp_params* P, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                                         const double* Rt_init, float trim_ratio, int32_t max_concurrent, ghicp_gicp_result* out) {
+  GH_ENTER(ctx);
+  return gicp_clouds_impl<true>(ctx, "ghicp_gicp_clouds_trimmed", P, n_pairs, S, T, Rt_init, trim_ratio, max_concurrent, out);
 }

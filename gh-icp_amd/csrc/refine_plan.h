@@ -47,3 +47,9 @@ constexpr size_t kGicpPointBytes = kRefinePointBytes + 48;
 inline std::vector<int> gh_gicp_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget) {
   return gh_refine_plan(n_pairs, ns, max_concurrent, budget, kGicpPairBytes, kGicpPointBytes);
 }
+
+// ghicp_gicp_clouds_trimmed: per pair the radix-select histograms of the ICP loop on top of that (its select record is within the 1024).
+constexpr size_t kGicpTrimPairBytes = kGicpPairBytes + 6 * 2048 * 4;
+inline std::vector<int> gh_gicp_trim_plan(int n_pairs, const int64_t* ns, int max_concurrent, size_t budget) {
+  return gh_refine_plan(n_pairs, ns, max_concurrent, budget, kGicpTrimPairBytes, kGicpPointBytes);
+}

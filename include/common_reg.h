@@ -7,6 +7,7 @@
 //                  Gauss-Newton inner solver (ghicp_c.h: ghicp_gicp).  use_reciprocal_correspondence has no
 //                  effect and use_trimmed_rejector is only the overlap gate, as in the reference (PCL's GICP never consults
 //                  the rejector, common_reg.cpp:213-215)
+//   trimmed_gicp_reg   (no counterpart) gicp_reg with the trimmed rejector applied (ghicp_c.h: ghicp_gicp_trimmed_from)
 //   calOverlap     common_reg.cpp:294-317
 //   transformcloud common_reg.cpp:325-349
 //   invTransform   common_reg.cpp:357-370   (R^T with the negated translation -- "Not Mathimatically" an inverse)
@@ -45,33 +46,18 @@ template <typename PointT> class CRegistration {
   bool gicp_reg(const typename pcl::PointCloud<PointT>::Ptr& SourceCloud, const typename pcl::PointCloud<PointT>::Ptr& TargetCloud,
                 typename pcl::PointCloud<PointT>::Ptr& TransformedSource, Eigen::Matrix4f& transformationS2T, int max_iter,
                 bool use_reciprocal_correspondence, bool use_trimmed_rejector, float thre_dis, int covariance_K, float min_overlap_for_reg) {
-    const clock_t t0 = clock();
-    ghicp_gicp_params p;
-    ghicp_gicp_params_default(&p);  // max correspondence distance 1e6, epsilons 1e-8 / 1e-6 (common_reg.cpp:253-265)
-    p.max_iter = max_iter;
-    p.use_reciprocal = use_reciprocal_correspondence ? 1 : 0;
-    p.use_trimmed = use_trimmed_rejector ? 1 : 0;
-    p.thre_dis = thre_dis;
-    p.min_overlap = min_overlap_for_reg;
-    p.covariance_k = covariance_K;
-    const size_t n = SourceCloud->points.size();
-    std::vector<float> xyz(n * 3 + 3);
-    float T16[16];
-    detail::check(ghicp_gicp(detail::ctx(), detail::xyz(*SourceCloud), (int64_t)n, detail::stride<PointT>(), detail::xyz(*TargetCloud),
-                             (int64_t)TargetCloud->points.size(), detail::stride<PointT>(), &p, T16, xyz.data(), &last_stats));
-    if (!last_stats.done) {
-      std::cout << "The overlap ratio is too small. This registration would not be done." << std::endl;  // common_reg.cpp:243-245
-      return false;
-    }
-    TransformedSource->points.clear();  // gicp.align(*TransformedSource) overwrites the output cloud
-    append_xyz(xyz, n, *TransformedSource);
-    for (int r = 0; r < 4; r++)
-      for (int c = 0; c < 4; c++) transformationS2T(r, c) = T16[r * 4 + c];
-    std::cout << "GICP done in " << float(clock() - t0) / CLOCKS_PER_SEC << " s" << std::endl;  // common_reg.cpp:281-283
-    for (int r = 0; r < 4; r++) std::cout << T16[r * 4] << " " << T16[r * 4 + 1] << " " << T16[r * 4 + 2] << " " << T16[r * 4 + 3] << std::endl;
-    std::cout << "The fitness score of this registration is " << last_stats.fitness << std::endl;
-    std::cout << "-----------------------------------------------------------------------------" << std::endl;
-    return true;
+    return run_gicp(false, SourceCloud, TargetCloud, TransformedSource, transformationS2T, max_iter, use_reciprocal_correspondence,
+                    use_trimmed_rejector, thre_dis, covariance_K, min_overlap_for_reg);
+  }
+
+  // gicp_reg with use_trimmed_rejector APPLIED (not in the reference, whose header announces it: "I am working on the G-ICP with trimmed
+  // property now"): every outer iteration keeps the share of the correspondences that calOverlap estimated, smallest distances first, as
+  // icp_reg does (ghicp_c.h: ghicp_gicp_trimmed_from with trim_ratio 0).  Without use_trimmed_rejector it is gicp_reg.
+  bool trimmed_gicp_reg(const typename pcl::PointCloud<PointT>::Ptr& SourceCloud, const typename pcl::PointCloud<PointT>::Ptr& TargetCloud,
+                        typename pcl::PointCloud<PointT>::Ptr& TransformedSource, Eigen::Matrix4f& transformationS2T, int max_iter,
+                        bool use_reciprocal_correspondence, bool use_trimmed_rejector, float thre_dis, int covariance_K, float min_overlap_for_reg) {
+    return run_gicp(use_trimmed_rejector, SourceCloud, TargetCloud, TransformedSource, transformationS2T, max_iter, use_reciprocal_correspondence,
+                    use_trimmed_rejector, thre_dis, covariance_K, min_overlap_for_reg);
   }
 
   float calOverlap(const typename pcl::PointCloud<PointT>::Ptr& Cloud1, const typename pcl::PointCloud<PointT>::Ptr& Cloud2, float thre_dis) {
@@ -278,6 +264,42 @@ template <typename PointT> class CRegistration {
     }
     cloud.width = (unsigned)cloud.points.size();
     cloud.height = 1;
+  }
+  // gicp_reg (apply_rejector false: common_reg.cpp:216-284) and trimmed_gicp_reg
+  bool run_gicp(bool apply_rejector, const typename pcl::PointCloud<PointT>::Ptr& SourceCloud, const typename pcl::PointCloud<PointT>::Ptr& TargetCloud,
+                typename pcl::PointCloud<PointT>::Ptr& TransformedSource, Eigen::Matrix4f& transformationS2T, int max_iter,
+                bool use_reciprocal_correspondence, bool use_trimmed_rejector, float thre_dis, int covariance_K, float min_overlap_for_reg) {
+    const clock_t t0 = clock();
+    ghicp_gicp_params p;
+    ghicp_gicp_params_default(&p);  // max correspondence distance 1e6, epsilons 1e-8 / 1e-6 (common_reg.cpp:253-265)
+    p.max_iter = max_iter;
+    p.use_reciprocal = use_reciprocal_correspondence ? 1 : 0;
+    p.use_trimmed = use_trimmed_rejector ? 1 : 0;
+    p.thre_dis = thre_dis;
+    p.min_overlap = min_overlap_for_reg;
+    p.covariance_k = covariance_K;
+    const size_t n = SourceCloud->points.size();
+    std::vector<float> xyz(n * 3 + 3);
+    float T16[16];
+    if (apply_rejector)  // ratio 0: the overlap the gate estimated
+      detail::check(ghicp_gicp_trimmed_from(detail::ctx(), detail::xyz(*SourceCloud), (int64_t)n, detail::stride<PointT>(), detail::xyz(*TargetCloud),
+                                            (int64_t)TargetCloud->points.size(), detail::stride<PointT>(), &p, nullptr, 0.f, T16, xyz.data(), &last_stats));
+    else
+      detail::check(ghicp_gicp(detail::ctx(), detail::xyz(*SourceCloud), (int64_t)n, detail::stride<PointT>(), detail::xyz(*TargetCloud),
+                               (int64_t)TargetCloud->points.size(), detail::stride<PointT>(), &p, T16, xyz.data(), &last_stats));
+    if (!last_stats.done) {
+      std::cout << "The overlap ratio is too small. This registration would not be done." << std::endl;  // common_reg.cpp:243-245
+      return false;
+    }
+    TransformedSource->points.clear();  // gicp.align(*TransformedSource) overwrites the output cloud
+    append_xyz(xyz, n, *TransformedSource);
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) transformationS2T(r, c) = T16[r * 4 + c];
+    std::cout << "GICP done in " << float(clock() - t0) / CLOCKS_PER_SEC << " s" << std::endl;  // common_reg.cpp:281-283
+    for (int r = 0; r < 4; r++) std::cout << T16[r * 4] << " " << T16[r * 4 + 1] << " " << T16[r * 4 + 2] << " " << T16[r * 4 + 3] << std::endl;
+    std::cout << "The fitness score of this registration is " << last_stats.fitness << std::endl;
+    std::cout << "-----------------------------------------------------------------------------" << std::endl;
+    return true;
   }
   bool run(int metric, const char* name, const typename pcl::PointCloud<PointT>::Ptr& S, const typename pcl::PointCloud<PointT>::Ptr& T,
            typename pcl::PointCloud<PointT>::Ptr& out, Eigen::Matrix4f& S2T, int max_iter, bool reciprocal, bool trimmed, float thre_dis, int cov_k,

@@ -379,7 +379,8 @@ int ghicp_transform_cloud_f32(ghicp_ctx* ctx, const float* xyz, int64_t n, int s
  *                (GHICP_ICP_TRANSFORM)
  *   output       final = transformation_, transformed = final * S, fitness = getFitnessScore()
  * GICP's computeTransformation does its own 1-NN search: the reference's reciprocal flag has no effect and its trimmed rejector is
- * never consulted (common_reg.cpp:213-215).  use_trimmed therefore acts only as the overlap gate (refusal below min_overlap). */
+ * never consulted (common_reg.cpp:213-215).  use_trimmed therefore acts only as the overlap gate (refusal below min_overlap); the calls that
+ * do apply the rejector are separate entry points (ghicp_gicp_trimmed_from, ghicp_gicp_clouds_trimmed). */
 typedef struct ghicp_gicp_params {
   int32_t max_iter;        /* gicp_reg argument */
   int32_t use_reciprocal;  /* accepted, no effect (see above) */
@@ -417,6 +418,23 @@ int ghicp_gicp(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const
 int ghicp_gicp_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
                     const ghicp_gicp_params* params, const float* guess16 /*[host] row-major 4x4, NULL = identity*/,
                     float* T16 /*[host]*/, float* transformed, ghicp_icp_stats* stats /*[host]*/);
+
+/* ghicp_gicp_from with the trimmed rejector APPLIED (opt-in; the reference's gicp_reg takes use_trimmed_rejector but PCL's GICP never
+ * consults it, and ghicp_gicp / ghicp_gicp_from / ghicp_gicp_clouds keep that: there use_trimmed is the gate alone).  Every outer iteration:
+ *   1. the source under transformation_;  2. its 1-NN in the target;
+ *   3. correspondences with d^2 >= max_correspondence_distance^2 are rejected; the survivors are `count`;
+ *   4. of those, the nv = min(count, floor(ratio * float(count))) smallest by the key (float d^2 bits, source index) are kept -- the rule and
+ *      the tie-break of ghicp_icp's trimmed rejector (CorrespondenceRejectorTrimmed): ranked by Euclidean d^2, not by Mahalanobis distance;
+ *   5. M_i, the count and the MSE over the kept set only;
+ *   6. nv < 4: GHICP_ICP_NO_CORRESPONDENCES, as ghicp_gicp_from for count < 4 (T16 = the guess when it happens in the first iteration).
+ * ratio is fixed for the whole registration, as in icp_reg: trim_ratio in (0, 1] is used as given; trim_ratio == 0 means the calOverlap
+ * estimate of the gate (this is how icp_reg feeds its rejector) and requires params->use_trimmed = 1.  stats->correspondences and stats->mse
+ * describe the kept set of the last iteration.  The inner solver, the convergence test, the fitness, the guess and the gate are those of
+ * ghicp_gicp_from; trim_ratio == 1 is ghicp_gicp_from itself, bit for bit.
+ * GHICP_ERR_ARG as ghicp_gicp_from, and for a trim_ratio that is negative, above 1 or not finite, or 0 without use_trimmed. */
+int ghicp_gicp_trimmed_from(ghicp_ctx* ctx, const float* xyzS, int64_t ns, int strideS, const float* xyzT, int64_t nt, int strideT,
+                            const ghicp_gicp_params* params, const float* guess16 /*[host] row-major 4x4, NULL = identity*/, float trim_ratio,
+                            float* T16 /*[host]*/, float* transformed, ghicp_icp_stats* stats /*[host]*/);
 
 /* The regularised covariances of one cloud as ghicp_gicp computes them: n x 6 f64 (c00, c01, c02, c11, c12, c22). k in 1..20. */
 int ghicp_gicp_covariances(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, int k, double eps, double* cov6);
@@ -527,6 +545,15 @@ typedef struct ghicp_gicp_result {
  * The handles are const.  max_concurrent as in ghicp_refine_clouds.  out: n_pairs [host]. */
 int ghicp_gicp_clouds(ghicp_ctx* ctx, const ghicp_gicp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
                       const double* Rt_init /*[host] n_pairs x 16, NULL = identity*/, int32_t max_concurrent, ghicp_gicp_result* out /*[host]*/);
+
+/* ghicp_gicp_clouds with the trimmed rejector applied: pair p comes out as ghicp_gicp_trimmed_from(down-sampled S[p], down-sampled T[p],
+ * params, float(Rt_init[p]), trim_ratio) gives it, bit for bit (T and every field of stats), whatever the other pairs do and whatever
+ * max_concurrent is.  trim_ratio == 0 (requires params->use_trimmed = 1): every pair keeps the share its OWN gate overlap estimates.
+ * Preparation, argument checks, refusal and chunking are those of ghicp_gicp_clouds, plus GHICP_ERR_ARG for a trim_ratio that is negative,
+ * above 1 or not finite, or 0 without use_trimmed.  48 KB of histograms per pair of a chunk on top of ghicp_gicp_clouds' buffers. */
+int ghicp_gicp_clouds_trimmed(ghicp_ctx* ctx, const ghicp_gicp_params* params, int32_t n_pairs, const ghicp_cloud* const* S, const ghicp_cloud* const* T,
+                              const double* Rt_init /*[host] n_pairs x 16, NULL = identity*/, float trim_ratio, int32_t max_concurrent,
+                              ghicp_gicp_result* out /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------------
  * calOverlap over cached clouds: which of MANY pairs of handles overlap at all under given poses -- CRegistration::calOverlap
