@@ -6,8 +6,10 @@
 // Here the clouds of a batch are CONCATENATED: every elementwise kernel, sort and select runs once over all their points, and the kernels
 // that work per cell / per keypoint (gh_pca_cell_body, gh_bsc_keypoint -- the same device code as the single-cloud path) look their cloud
 // up in a descriptor block.
-//   * voxel keys carry the cloud id above the voxel key's bits  -> one stable radix sort keeps clouds apart and ordered;
-//   * grid cells are numbered globally (cell base of the cloud + cell) -> one sort / one cell table per grid for all clouds;
+//   * voxel keys carry the cloud id above the voxel key's bits; the clouds are the segments of ONE stable radix sort (prims.hip: every cloud
+//     sorted among its own points inside the same launches, on the voxel key's bits alone), so clouds stay apart and ordered;
+//   * grid cells are numbered globally (cell base of the cloud + cell) -> one segmented sort (on the cell inside the cloud's grid) / one cell
+//     table per grid for all clouds;
 //   * NMS: decision rounds with one thread per candidate over every cloud of the batch, not the one-workgroup sweep of the single-cloud
 //     path (batch_nms.hip has the design).
 // FPFH clouds: the kNN grid is the batch's second grid and the normal / SPFH / FPFH kernels of fpfh.hip run once over the concatenated cloud.
@@ -70,19 +72,34 @@ __global__ __launch_bounds__(256) void k_fb_bbox(const FbBlock* __restrict__ D, 
 // filter.hpp:57-70 per cloud; the cloud id sits above the voxel key's bits
 // idx_bits > 0 (branch next/fe-packed-voxel-sort): the point's index rides in the low bits of the key itself -- ONE 8-byte array goes through the
 // radix sort (keys only, sorted on the bits above the index: stable, so the lowest index still leads its voxel) instead of a key and a value array
-__global__ __launch_bounds__(256) void k_fb_voxel_keys(const FbBlock* __restrict__ D, int N, int shift, int idx_bits, unsigned long long* __restrict__ keys,
-                                                       unsigned* __restrict__ vals) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  const int b = fb_find(D->roff, D->nb, i);
+// One workgroup per tile of the voxel sort's partition (sort_plan.h: tiles never cross a cloud, so the tile's segment IS the cloud); F.table != nullptr:
+// the tile's counts of the sort's first digit place are taken on the way (gh_rs_first_*, prims.h) and the sort skips its first histogram pass
+__global__ __launch_bounds__(256) void k_fb_voxel_keys(const FbBlock* __restrict__ D, GhRsSegs S, int shift, int idx_bits, unsigned long long* __restrict__ keys,
+                                                       unsigned* __restrict__ vals, GhRsFirst F) {
+  __shared__ unsigned cnt[4][GH_RS_MAX_ND];
+  const bool hist = F.table != nullptr;
+  if (hist) gh_rs_first_zero(cnt, F.nd);
+  const GhRsTile t = gh_rs_tile(S, (int)blockIdx.x);
+  const int b = t.seg;
   const FbCloud& C = D->c[b];
-  const float* p = C.xyz + (size_t)(i - D->roff[b]) * C.stride;
-  const unsigned long long vx = (unsigned long long)floorf((p[0] - C.vmn[0]) * C.vinv);
-  const unsigned long long vy = (unsigned long long)floorf((p[1] - C.vmn[1]) * C.vinv);
-  const unsigned long long vz = (unsigned long long)floorf((p[2] - C.vmn[2]) * C.vinv);
-  const unsigned long long key = ((unsigned long long)b << shift) | (vx * C.mul_x + vy * C.mul_y + vz);
-  if (idx_bits > 0) keys[i] = (key << idx_bits) | (unsigned long long)i;
-  else { keys[i] = key; vals[i] = (unsigned)i; }
+  const float* base = C.xyz + (size_t)(t.first - S.off[b]) * C.stride;
+#pragma unroll 4
+  for (int k = 0; k < GH_RS_TILE / 256; k++) {
+    const int j = k * 256 + (int)threadIdx.x;
+    if (j < t.here) {
+      const int i = t.first + j;
+      const float* p = base + (size_t)j * C.stride;
+      const unsigned long long vx = (unsigned long long)floorf((p[0] - C.vmn[0]) * C.vinv);
+      const unsigned long long vy = (unsigned long long)floorf((p[1] - C.vmn[1]) * C.vinv);
+      const unsigned long long vz = (unsigned long long)floorf((p[2] - C.vmn[2]) * C.vinv);
+      const unsigned long long vox = vx * C.mul_x + vy * C.mul_y + vz;
+      const unsigned long long key = ((unsigned long long)b << shift) | vox;
+      if (idx_bits > 0) keys[i] = (key << idx_bits) | (unsigned long long)i;
+      else { keys[i] = key; vals[i] = (unsigned)i; }
+      if (hist) gh_rs_first_add(cnt, (unsigned)vox & F.mask);
+    }
+  }
+  if (hist) gh_rs_first_store(cnt, F, (int)blockIdx.x);
 }
 
 // head of every voxel run whose voxel key > 0 (the run of voxel 0 is the reference's phantom group: filter.hpp:52,66,75-83)
@@ -141,18 +158,32 @@ __global__ __launch_bounds__(256) void k_fb_gather_ds(const FbBlock* __restrict_
   dsg[i] = make_float4(p[0], p[1], p[2], 0.f);
 }
 
-__global__ __launch_bounds__(256) void k_fb_cell_keys(const FbBlock* __restrict__ D, int which, const float4* __restrict__ dsg, int M,
-                                                      unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
-  const int b = fb_find(D->moff, D->nb, i);
+// one workgroup per tile of the grid sort's partition (the tile's segment is the cloud); the first place's counts as in k_fb_voxel_keys
+__global__ __launch_bounds__(256) void k_fb_cell_keys(const FbBlock* __restrict__ D, int which, const float4* __restrict__ dsg, GhRsSegs S,
+                                                      unsigned* __restrict__ keys, unsigned* __restrict__ vals, GhRsFirst F) {
+  __shared__ unsigned cnt[4][GH_RS_MAX_ND];
+  const bool hist = F.table != nullptr;
+  if (hist) gh_rs_first_zero(cnt, F.nd);
+  const GhRsTile t = gh_rs_tile(S, (int)blockIdx.x);
+  const int b = t.seg;
   const GridDesc& g = which ? D->g2[b] : D->g1[b];
-  const float4 P = dsg[i];
-  const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
-  const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
-  const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
-  keys[i] = (which ? D->cb2[b] : D->cb1[b]) + (((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz);
-  vals[i] = (unsigned)i;
+  const unsigned cb = which ? D->cb2[b] : D->cb1[b];
+#pragma unroll 4
+  for (int k = 0; k < GH_RS_TILE / 256; k++) {
+    const int j = k * 256 + (int)threadIdx.x;
+    if (j < t.here) {
+      const int i = t.first + j;
+      const float4 P = dsg[i];
+      const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
+      const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
+      const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
+      const unsigned cell = ((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz;
+      keys[i] = cb + cell;
+      vals[i] = (unsigned)i;
+      if (hist) gh_rs_first_add(cnt, cell & F.mask);
+    }
+  }
+  if (hist) gh_rs_first_store(cnt, F, (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_fb_gather_sorted(const float4* __restrict__ dsg, const unsigned* __restrict__ vals, int M, float4* __restrict__ pts) {
@@ -285,8 +316,8 @@ void decode_box(const int* enc, float* mm) {
 }
 
 // one grid of the batch: global cell keys -> stable sort -> points in cell order -> cell table
-int build_grid(ghicp_ctx* ctx, const FbBlock* D, int which, const float4* dsg, int M, unsigned total_cells, const GridSlots& sl, const float4** pts_out,
-               const unsigned** start_out, const unsigned** keys_out) {
+int build_grid(ghicp_ctx* ctx, const FbBlock* D, const FbBlock* H, int which, const float4* dsg, int M, unsigned total_cells, const GridSlots& sl,
+               const float4** pts_out, const unsigned** start_out, const unsigned** keys_out) {
   hipStream_t s = ctx->stream;
   unsigned *keys, *keys2, *vals, *vals2, *start;
   float4* pts;
@@ -297,8 +328,22 @@ int build_grid(ghicp_ctx* ctx, const FbBlock* D, int which, const float4* dsg, i
   GH_TRY(ctx->reserve(sl.start, (size_t)total_cells + 2, &start));
   GH_TRY(ctx->reserve(sl.pts, (size_t)M + 1, &pts));
   hipEvent_t kg = ctx->kt_begin(KT_FB_GRID);
-  hipLaunchKernelGGL(k_fb_cell_keys, dim3(cdiv(M, 256)), dim3(256), 0, s, D, which, dsg, M, keys, vals);
-  GH_TRY(gh_radix_sort_u32(ctx, keys, keys2, vals, vals2, M, 0, bits_for(total_cells)));  // stable: a cell keeps its points in down-sampled order (prims.hip)
+  // stable: a cell keeps its points in down-sampled order (prims.hip).  The down-sampled clouds are the sort's segments: a cloud's points are
+  // sorted on the cell inside the cloud's own grid (key - cell base), so the bits are those of the largest grid, not of all grids together.
+  // The key kernel runs over the sort's tiles and leaves the first place's counts where the sort wants them.
+  int cell_bits = 0;
+  for (int b = 0; b < H->nb; b++) {
+    const unsigned ncell = which ? H->g2[b].ncell : H->g1[b].ncell;
+    if (H->moff[b + 1] > H->moff[b] && ncell > 1) cell_bits = std::max(cell_bits, bits_for(ncell - 1));
+  }
+  GhRsSort R;
+  GH_TRY(gh_rs_seg_begin(ctx, H->nb, H->moff, cell_bits, 0, &R));
+  if (ctx->sort_trace) fprintf(stderr, "sort_trace grid%d clouds=%d keys=%d bits_one_grid=%d bits_all_grids=%d places=%d\n", which + 1, H->nb, M, cell_bits, bits_for(total_cells), R.P.places);
+  if (!ctx->sort_segments) R.first.table = nullptr;
+  hipLaunchKernelGGL(k_fb_cell_keys, dim3(R.S.toff[R.S.nseg]), dim3(256), 0, s, D, which, dsg, R.S, keys, vals, R.first);
+  R.have_first = R.first.table != nullptr;
+  if (ctx->sort_segments) GH_TRY(gh_radix_sort_seg_u32(ctx, keys, keys2, vals, vals2, R, which ? D->cb2 : D->cb1, 0));
+  else GH_TRY(gh_radix_sort_u32(ctx, keys, keys2, vals, vals2, M, 0, bits_for(total_cells)));
   hipLaunchKernelGGL(k_fb_gather_sorted, dim3(cdiv(M, 256)), dim3(256), 0, s, dsg, vals2, M, pts);
   gh_cell_start_launch(s, keys2, (unsigned)M, total_cells, start);  // (round 5: the table is filled from the sorted keys, grid.hip)
   ctx->kt_end(KT_FB_GRID, kg);
@@ -397,12 +442,21 @@ int FbRun::voxel() {
   int idx_bits = 1;
   while ((1ll << idx_bits) < N) idx_bits++;
   if (ebmax + cloud_bits + idx_bits > 64) idx_bits = 0;
-  hipLaunchKernelGGL(k_fb_voxel_keys, dim3(cdiv(N, 256)), dim3(256), 0, s, (const FbBlock*)D, (int)N, ebmax, idx_bits, vkeys, vvals);
+  // the raw clouds are the sort's segments: a cloud's points are sorted among themselves on the voxel key's bits alone, the id above them rides
+  // along; the key kernel runs over the sort's tiles and leaves the first place's counts where the sort wants them
+  GhRsSort R;
+  GH_TRY(gh_rs_seg_begin(ctx, nb, H->roff, ebmax, 0, &R));
+  if (ctx->sort_trace) fprintf(stderr, "sort_trace voxel clouds=%d keys=%lld voxel_bits=%d cloud_id_bits=%d places=%d\n", nb, N, ebmax, cloud_bits, R.P.places);
+  if (!ctx->sort_segments) R.first.table = nullptr;
+  hipLaunchKernelGGL(k_fb_voxel_keys, dim3(R.S.toff[R.S.nseg]), dim3(256), 0, s, (const FbBlock*)D, R.S, ebmax, idx_bits, vkeys, vvals, R.first);
+  R.have_first = R.first.table != nullptr;
   ctx->kt_end(KT_FB_VOXEL, kv0);
   const int sort_bits = ebmax + cloud_bits;
   hipEvent_t kev = ctx->kt_begin(KT_VOXEL_SORT);
   // stable: lowest index leads its voxel (prims.hip)
-  if (idx_bits > 0) GH_TRY(gh_radix_sort_u64(ctx, vkeys, vkeys2, nullptr, nullptr, N, idx_bits, idx_bits + sort_bits));
+  if (ctx->sort_segments && idx_bits > 0) GH_TRY(gh_radix_sort_seg_u64(ctx, vkeys, vkeys2, nullptr, nullptr, R, idx_bits));
+  else if (ctx->sort_segments) GH_TRY(gh_radix_sort_seg_u64(ctx, vkeys, vkeys2, vvals, vvals2, R, 0));
+  else if (idx_bits > 0) GH_TRY(gh_radix_sort_u64(ctx, vkeys, vkeys2, nullptr, nullptr, N, idx_bits, idx_bits + sort_bits));
   else GH_TRY(gh_radix_sort_u64(ctx, vkeys, vkeys2, vvals, vvals2, N, 0, sort_bits));
   ctx->kt_end(KT_VOXEL_SORT, kev);
   const unsigned long long vmask = ebmax >= 64 ? ~0ull : ((1ull << ebmax) - 1ull);
@@ -469,7 +523,7 @@ int FbRun::pca_prune() {
   const float4* pts1;
   const unsigned *start1, *keys1;
   const GridSlots sl1 = {B_GRID_KEYS, B_GRID_KEYS2, B_GRID_VALS, B_GRID_VALS2, B_GRID_START, B_GRID_PTS};
-  GH_TRY(build_grid(ctx, D, 0, dsg, M, (unsigned)t1, sl1, &pts1, &start1, &keys1));
+  GH_TRY(build_grid(ctx, D, H, 0, dsg, M, (unsigned)t1, sl1, &pts1, &start1, &keys1));
   hipEvent_t ku = ctx->kt_begin(KT_FB_GRID);
   GH_TRY(gh_unique_sorted_u32(ctx, keys1, M, cells, misc));  // the occupied cells, ascending (prims.hip)
   GH_HIP(hipMemsetAsync(misc + 4, 0, 8 * sizeof(int), s));
@@ -528,7 +582,7 @@ int FbRun::features(const BscConst& BC) {
     const float4* pts2;
     const unsigned *start2, *keys2;
     const GridSlots sl2 = {B_GRID2_KEYS, B_GRID2_KEYS2, B_GRID2_VALS, B_GRID2_VALS2, B_GRID2_START, B_GRID2_PTS};
-    GH_TRY(build_grid(ctx, D, 1, dsg, M, (unsigned)t2, sl2, &pts2, &start2, &keys2));
+    GH_TRY(build_grid(ctx, D, H, 1, dsg, M, (unsigned)t2, sl2, &pts2, &start2, &keys2));
     if (bsc) {
       hipEvent_t kb = ctx->kt_begin(KT_BSC);
       hipLaunchKernelGGL(k_fb_bsc, dim3((unsigned)Ktot), dim3(BT), 0, s, (const FbBlock*)D, pts2, start2, BC, lcs);

@@ -196,6 +196,14 @@ struct ghicp_ctx {
   // planning of round 6: A/B measurements); GHICP_KM_COMPACT_FROM=<n> is the test hook that FORCES the compact layout on every graph of n rows
   // or more (1: on every graph), whatever LDS its slot has.
   bool km_compact = true;
+  // Segmented radix sort of the batched front end (prims.hip, sort_plan.h: no cloud id among the sorted bits, places planned from the bits
+  // present).  GHICP_SORT_SEGMENTS=0 takes the one sort over id and key of round 6 (A/B measurements); GHICP_SORT_DIGIT_BITS=8 keeps every
+  // digit at 8 bits (only the cloud id's places are dropped).
+  bool sort_segments = true;
+  int sort_digit_bits = 9;
+  bool sort_trace = false;       // GHICP_SORT_TRACE: a line on stderr per batched sort (clouds, keys, key bits, places)
+  bool sort_hist_check = false;  // test hook (ghicp_ctx_set_sort_hist_check): counts left by a key-making kernel against the keys' own
+  long long sort_hist_checked = 0, sort_hist_mismatched = 0;
   int km_compact_from = 0;
   int km_kflags() const { return (km_force_hazard ? 4 : 0) | (km_compact_from << 8); }  // the solver's flag word (k4_solve_block)
   // Persistent pair loop: ONE combined-distance pass per iteration decides the graph's membership while it takes the sums behind CDmean / CDstd

@@ -43,6 +43,9 @@ extern "C" int ghicp_ctx_create(int device, ghicp_ctx** out) {
   if (const char* e = getenv("GHICP_LOOP_CONFINE")) c->loop_confine = atoi(e) != 0;
   if (const char* e = getenv("GHICP_KM_COMPACT")) c->km_compact = atoi(e) != 0;
   if (const char* e = getenv("GHICP_LOOP_FUSE")) c->loop_fuse = atoi(e) != 0;
+  c->sort_trace = getenv("GHICP_SORT_TRACE") != nullptr;
+  if (const char* e = getenv("GHICP_SORT_SEGMENTS")) c->sort_segments = atoi(e) != 0;
+  if (const char* e = getenv("GHICP_SORT_DIGIT_BITS")) c->sort_digit_bits = atoi(e) == 8 ? 8 : 9;
   if (const char* e = getenv("GHICP_KM_COMPACT_FROM")) c->km_compact_from = atoi(e) > 0 && atoi(e) < 65535 ? atoi(e) : 0;
   if (const char* e = getenv("GHICP_LOOP_MIN_LDS")) c->loop_min_lds = atoi(e) > 0 ? atoi(e) : 0;
   if (const char* e = getenv("GHICP_LOOP_CONFINE_MARGIN")) { const double m = atof(e); if (m >= 0.25 && m <= 4.0) c->loop_confine_margin = m; }  // experiment hook: margin on the confined class's share

@@ -10,6 +10,8 @@
 #include "prims.h"
 
 #include <algorithm>
+#include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -231,28 +233,37 @@ __global__ __launch_bounds__(RD) void k_rs_bases(unsigned* __restrict__ part, in
 // T.lk / T.lv in stable order of the digit, T.first[d] = first position of digit d.  Ranks from wave ballots: a wave owns PI * 64 consecutive
 // items and takes them 64 at a time; the lanes of a round that share a digit find each other with eight ballots, the lowest of them bumps the
 // wave's counter of that digit (LDS, that one lane only) and hands the old value round.  Ends with a barrier.
-template <typename K, bool HASV>
+// ND digits per place: 256, or 512 for the 9-bit places of the segmented sort (sort_plan.h).  No count exceeds the tile's 4096 items, so the 512
+// counters are u16: the tile stays at 39 KB of LDS, four workgroups to a CU as with 256.  `kbase` is taken off the key before the digit (the
+// segmented sort of global cell keys; 0 elsewhere).
+template <typename K, bool HASV, int ND = 256>
 struct RsTile {
-  unsigned cnt[4][RD];  // per wave: running count of a digit, then the wave's base inside the digit's run of this tile
-  unsigned first[RD];
+  typedef typename std::conditional<(ND > 256), unsigned short, unsigned>::type C;
+  C cnt[4][ND];  // per wave: running count of a digit, then the wave's base inside the digit's run of this tile
+  C first[ND];
   unsigned sh[4];
   K lk[TILE];
   unsigned lv[HASV ? TILE : 1];
 };
-template <typename K, bool HASV>
-__device__ inline void rs_tile_sort(RsTile<K, HASV>& T, const K (&key)[PI], const unsigned (&val)[PI], int here, int shift, unsigned mask) {
+template <typename K, bool HASV, int ND = 256>
+__device__ inline void rs_tile_sort(RsTile<K, HASV, ND>& T, const K (&key)[PI], const unsigned (&val)[PI], int here, int shift, unsigned mask, K kbase = (K)0) {
+  constexpr int DPT = ND / PT;  // digits per thread where thread = digit: DPT consecutive ones
+  constexpr int NB = ND > 256 ? 9 : 8;
+  typedef typename RsTile<K, HASV, ND>::C C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int w = 0; w < 4; w++) T.cnt[w][threadIdx.x] = 0u;
+  for (int w = 0; w < 4; w++)
+#pragma unroll
+    for (int q = 0; q < DPT; q++) T.cnt[w][q * PT + threadIdx.x] = (C)0;
   __syncthreads();
   unsigned rk[PI];
 #pragma unroll
   for (int k = 0; k < PI; k++) {
     const bool valid = (wave * PI + k) * 64 + lane < here;
-    const unsigned d = (unsigned)(key[k] >> shift) & mask;
+    const unsigned d = (unsigned)((key[k] - kbase) >> shift) & mask;
     unsigned long long peers = __ballot(valid);
 #pragma unroll
-    for (int b = 0; b < 8; b++) {
+    for (int b = 0; b < NB; b++) {
       const bool bit = (d >> b) & 1u;
       const unsigned long long m = __ballot(bit);
       peers &= bit ? m : ~m;
@@ -261,25 +272,36 @@ __device__ inline void rs_tile_sort(RsTile<K, HASV>& T, const K (&key)[PI], cons
     unsigned base = 0;
     if (valid && lane == leader) {
       base = T.cnt[wave][d];
-      T.cnt[wave][d] = base + (unsigned)__popcll(peers);
+      T.cnt[wave][d] = (C)(base + (unsigned)__popcll(peers));
     }
     base = __shfl(base, leader, 64);
     rk[k] = base + (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
   }
   __syncthreads();
   {  // thread = digit: the waves' bases inside the digit's run, the run's place in the tile
-    const int d = threadIdx.x;
-    const unsigned c0 = T.cnt[0][d], c1 = T.cnt[1][d], c2 = T.cnt[2][d], c3 = T.cnt[3][d];
-    T.cnt[0][d] = 0u; T.cnt[1][d] = c0; T.cnt[2][d] = c0 + c1; T.cnt[3][d] = c0 + c1 + c2;
+    unsigned sum[DPT], all = 0;
+#pragma unroll
+    for (int q = 0; q < DPT; q++) {
+      const int d = threadIdx.x * DPT + q;
+      const unsigned c0 = T.cnt[0][d], c1 = T.cnt[1][d], c2 = T.cnt[2][d], c3 = T.cnt[3][d];
+      T.cnt[0][d] = (C)0; T.cnt[1][d] = (C)c0; T.cnt[2][d] = (C)(c0 + c1); T.cnt[3][d] = (C)(c0 + c1 + c2);
+      sum[q] = c0 + c1 + c2 + c3;
+      all += sum[q];
+    }
     unsigned tot;
-    T.first[d] = block_excl_scan(c0 + c1 + c2 + c3, T.sh, &tot);
+    unsigned run = block_excl_scan(all, T.sh, &tot);
+#pragma unroll
+    for (int q = 0; q < DPT; q++) {
+      T.first[threadIdx.x * DPT + q] = (C)run;
+      run += sum[q];
+    }
   }
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < PI; k++) {
     if ((wave * PI + k) * 64 + lane < here) {
-      const unsigned d = (unsigned)(key[k] >> shift) & mask;
-      const unsigned p = T.first[d] + T.cnt[wave][d] + rk[k];
+      const unsigned d = (unsigned)((key[k] - kbase) >> shift) & mask;
+      const unsigned p = (unsigned)T.first[d] + (unsigned)T.cnt[wave][d] + rk[k];
       T.lk[p] = key[k];
       if (HASV) T.lv[p] = val[k];
     }
@@ -453,7 +475,301 @@ int radix_sort_impl(ghicp_ctx* ctx, const K* kin, K* kout, const unsigned* vin, 
   return GHICP_OK;
 }
 
+// ================================================================================ segmented places (sort_plan.h)
+// The clouds of a launch sequence sorted cloud by cloud inside the same launches: a tile lies in one segment, the counts are kept per (segment,
+// place, tile) and scanned per segment, so the segment's id is not among the sorted bits -- 34 instead of 39 bits for the packed voxel keys of 32
+// clouds, and digits of up to 9 bits make that four places.  The segments travel as a kernel argument (GhRsSegs): a workgroup finds its tile's
+// segment with a binary search over scalar loads.  Launches per place: k_rss_hist, k_rss_chunks, k_rss_bases, k_rss_scatter; three when no segment
+// has more than one chunk (k_rss_bases walks the tiles itself); ONE for all places when no segment has more than one tile (k_rss_small).
+static_assert(TILE == GH_RS_TILE && RC == GH_RS_CHUNK, "sort_plan.h defines the tile partition");
 
+// (gh_rs_find / gh_rs_tile: prims.h, shared with the kernels that make the keys and may leave the first place's counts: GhRsFirst)
+
+template <typename K, int ND>
+__global__ __launch_bounds__(PT) void k_rss_hist(const K* __restrict__ keys, GhRsSegs S, const unsigned* __restrict__ kbase, int shift, unsigned mask,
+                                                 unsigned* __restrict__ table) {
+  __shared__ unsigned cnt[4][ND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int w = 0; w < 4; w++)
+#pragma unroll
+    for (int q = 0; q < ND / PT; q++) cnt[w][q * PT + threadIdx.x] = 0u;
+  __syncthreads();
+  const GhRsTile t = gh_rs_tile(S, (int)blockIdx.x);
+  const K kb = kbase ? (K)kbase[t.seg] : (K)0;
+  K key[PI];
+#pragma unroll
+  for (int k = 0; k < PI; k++) {
+    const int j = (wave * PI + k) * 64 + lane;
+    key[k] = j < t.here ? keys[(size_t)t.first + j] : (K)0;
+  }
+#pragma unroll
+  for (int k = 0; k < PI; k++)
+    if ((wave * PI + k) * 64 + lane < t.here) atomicAdd(&cnt[wave][(unsigned)((key[k] - kb) >> shift) & mask], 1u);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < ND / PT; q++) {
+    const int d = q * PT + threadIdx.x;
+    table[(size_t)blockIdx.x * ND + d] = cnt[0][d] + cnt[1][d] + cnt[2][d] + cnt[3][d];
+  }
+}
+
+// thread = digit (and digit + 256): the tiles [t0, t1) in turn, their counts replaced by the running count before them
+template <int ND>
+__device__ inline void rss_walk(unsigned* __restrict__ table, int t0, int t1, unsigned (&run)[ND / PT]) {
+  // 16 rows' loads in flight: the walk is a chain of memory round trips, not of adds
+#pragma unroll 16
+  for (int t = t0; t < t1; t++)
+#pragma unroll
+    for (int q = 0; q < ND / PT; q++) {
+      const size_t at = (size_t)t * ND + q * PT + threadIdx.x;
+      const unsigned v = table[at];
+      table[at] = run[q];
+      run[q] += v;
+    }
+}
+
+template <int ND>
+__global__ __launch_bounds__(PT) void k_rss_chunks(unsigned* __restrict__ table, GhRsSegs S, unsigned* __restrict__ part) {
+  const int c = (int)blockIdx.x, seg = gh_rs_find(S.coff, S.nseg, c);
+  const int t0 = S.toff[seg] + (c - S.coff[seg]) * RC, t1 = t0 + RC < S.toff[seg + 1] ? t0 + RC : S.toff[seg + 1];
+  unsigned run[ND / PT] = {};
+  rss_walk<ND>(table, t0, t1, run);
+#pragma unroll
+  for (int q = 0; q < ND / PT; q++) part[(size_t)c * ND + q * PT + threadIdx.x] = run[q];
+}
+
+// One workgroup per segment: the chunks' totals -> part[chunk][digit] = items of the segment with a lower digit + items of that digit in the
+// segment's chunks before.  walk: the segment is one chunk whose tiles this kernel walks itself (no k_rss_chunks before it).
+template <int ND>
+__global__ __launch_bounds__(PT) void k_rss_bases(unsigned* __restrict__ table, unsigned* __restrict__ part, GhRsSegs S, int walk) {
+  constexpr int DPT = ND / PT;
+  __shared__ unsigned sh[4];
+  __shared__ unsigned dig[ND];
+  const int s = (int)blockIdx.x, c0 = S.coff[s], c1 = S.coff[s + 1];
+  if (c0 == c1) return;  // an empty segment
+  unsigned run[DPT] = {};
+  if (walk) rss_walk<ND>(table, S.toff[s], S.toff[s + 1], run);
+  else
+    for (int c = c0; c < c1; c++)
+#pragma unroll
+      for (int q = 0; q < DPT; q++) {
+        const size_t at = (size_t)c * ND + q * PT + threadIdx.x;
+        const unsigned v = part[at];
+        part[at] = run[q];
+        run[q] += v;
+      }
+#pragma unroll
+  for (int q = 0; q < DPT; q++) dig[q * PT + threadIdx.x] = run[q];
+  __syncthreads();
+  unsigned sum[DPT], all = 0;  // DPT consecutive digits per thread for the scan over the digits
+#pragma unroll
+  for (int q = 0; q < DPT; q++) { sum[q] = dig[threadIdx.x * DPT + q]; all += sum[q]; }
+  unsigned tot;
+  unsigned ex = block_excl_scan(all, sh, &tot);
+#pragma unroll
+  for (int q = 0; q < DPT; q++) { dig[threadIdx.x * DPT + q] = ex; ex += sum[q]; }
+  __syncthreads();
+  if (walk) {
+#pragma unroll
+    for (int q = 0; q < DPT; q++) part[(size_t)c0 * ND + q * PT + threadIdx.x] = dig[q * PT + threadIdx.x];
+  } else {
+    for (int c = c0; c < c1; c++)
+#pragma unroll
+      for (int q = 0; q < DPT; q++) part[(size_t)c * ND + q * PT + threadIdx.x] += dig[q * PT + threadIdx.x];
+  }
+}
+
+template <typename K, bool HASV, int ND>
+__global__ __launch_bounds__(PT) void k_rss_scatter(const K* __restrict__ kin, const unsigned* __restrict__ vin, K* __restrict__ kout, unsigned* __restrict__ vout,
+                                                    GhRsSegs S, const unsigned* __restrict__ kbase, int shift, unsigned mask, const unsigned* __restrict__ table,
+                                                    const unsigned* __restrict__ part) {
+  constexpr int DPT = ND / PT;
+  __shared__ RsTile<K, HASV, ND> T;
+  __shared__ unsigned s_delta[ND];  // global position of the digit's run of this tile - its first position in the tile
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const GhRsTile t = gh_rs_tile(S, (int)blockIdx.x);
+  const K kb = kbase ? (K)kbase[t.seg] : (K)0;
+  K key[PI];
+  unsigned val[PI];
+#pragma unroll
+  for (int k = 0; k < PI; k++) {
+    const int j = (wave * PI + k) * 64 + lane;
+    key[k] = j < t.here ? kin[(size_t)t.first + j] : (K)0;
+    val[k] = (HASV && j < t.here) ? vin[(size_t)t.first + j] : 0u;
+  }
+  const int chunk = S.coff[t.seg] + ((int)blockIdx.x - S.toff[t.seg]) / RC;
+  unsigned run_at[DPT];
+#pragma unroll
+  for (int q = 0; q < DPT; q++) {
+    const int d = q * PT + threadIdx.x;
+    run_at[q] = (unsigned)S.off[t.seg] + table[(size_t)blockIdx.x * ND + d] + part[(size_t)chunk * ND + d];
+  }
+  rs_tile_sort<K, HASV, ND>(T, key, val, t.here, shift, mask, kb);
+#pragma unroll
+  for (int q = 0; q < DPT; q++) {
+    const int d = q * PT + threadIdx.x;
+    s_delta[d] = run_at[q] - (unsigned)T.first[d];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < PI; j++) {
+    const int p = j * PT + threadIdx.x;
+    if (p < t.here) {
+      const K kk = T.lk[p];
+      const unsigned pos = s_delta[(unsigned)((kk - kb) >> shift) & mask] + (unsigned)p;
+      kout[pos] = kk;
+      if (HASV) vout[pos] = T.lv[p];
+    }
+  }
+}
+
+// no segment beyond one tile: every place in ONE launch, a workgroup per segment (k_rs_small per segment)
+template <typename K, bool HASV, int ND>
+__global__ __launch_bounds__(PT) void k_rss_small(const K* __restrict__ kin, const unsigned* __restrict__ vin, K* __restrict__ kout, unsigned* __restrict__ vout,
+                                                  GhRsSegs S, const unsigned* __restrict__ kbase, int bit_begin, GhRsPlan P) {
+  __shared__ RsTile<K, HASV, ND> T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = (int)blockIdx.x, n = S.off[s + 1] - S.off[s];
+  if (n <= 0) return;
+  const size_t at = (size_t)S.off[s];
+  const K kb = kbase ? (K)kbase[s] : (K)0;
+  K key[PI];
+  unsigned val[PI];
+#pragma unroll
+  for (int k = 0; k < PI; k++) {
+    const int i = (wave * PI + k) * 64 + lane;
+    key[k] = i < n ? kin[at + i] : (K)0;
+    val[k] = (HASV && i < n) ? vin[at + i] : 0u;
+  }
+  int shift = bit_begin;
+  for (int p = 0; p < P.places; p++) {
+    rs_tile_sort<K, HASV, ND>(T, key, val, n, shift, (1u << P.width[p]) - 1u, kb);
+    shift += P.width[p];
+    if (p + 1 < P.places) {
+#pragma unroll
+      for (int k = 0; k < PI; k++) {
+        const int i = (wave * PI + k) * 64 + lane;
+        if (i < n) {
+          key[k] = T.lk[i];
+          if (HASV) val[k] = T.lv[i];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < PI; j++) {
+    const int p = j * PT + threadIdx.x;
+    if (p < n) {
+      kout[at + p] = T.lk[p];
+      if (HASV) vout[at + p] = T.lv[p];
+    }
+  }
+}
+
+// one place.  first: the counts of this place are in the table already (GhRsFirst: the kernel that made the keys took them)
+template <typename K, bool HASV, int ND>
+void rss_place(hipStream_t s, const K* src_k, const unsigned* src_v, K* dst_k, unsigned* dst_v, const GhRsSegs& S, bool one_chunk, const unsigned* kbase, int shift,
+               unsigned mask, unsigned* table, unsigned* part, bool first) {
+  const int nt = S.toff[S.nseg], nchunk = S.coff[S.nseg];
+  if (!first) hipLaunchKernelGGL((k_rss_hist<K, ND>), dim3(nt), dim3(PT), 0, s, src_k, S, kbase, shift, mask, table);
+  if (!one_chunk) hipLaunchKernelGGL((k_rss_chunks<ND>), dim3(nchunk), dim3(PT), 0, s, table, S, part);
+  hipLaunchKernelGGL((k_rss_bases<ND>), dim3(S.nseg), dim3(PT), 0, s, table, part, S, one_chunk ? 1 : 0);
+  hipLaunchKernelGGL((k_rss_scatter<K, HASV, ND>), dim3(nt), dim3(PT), 0, s, src_k, src_v, dst_k, dst_v, S, kbase, shift, mask, (const unsigned*)table,
+                     (const unsigned*)part);
+}
+
+bool rs_wide(const GhRsPlan& P) {  // a 9-bit place among them
+  bool wide = false;
+  for (int p = 0; p < P.places; p++) wide = wide || P.width[p] > 8;
+  return wide;
+}
+// the table of a tiled sort: table[tile][nd], then part[chunk][nd] (nd: the widest place's)
+int rs_table(ghicp_ctx* ctx, const GhRsSort& R, unsigned** table, unsigned** part) {
+  const size_t nd = rs_wide(R.P) ? 512 : 256, nt = (size_t)R.S.toff[R.S.nseg], nchunk = (size_t)R.S.coff[R.S.nseg];
+  GH_TRY(ctx->reserve(B_PRIM_TMP, nt * nd + nchunk * nd + 4, table));
+  *part = *table + nt * nd;
+  return GHICP_OK;
+}
+
+// test hook (ghicp_ctx_set_sort_hist_check): the counts a key-making kernel left against k_rss_hist's over the same keys; synchronises
+template <typename K>
+int rs_check_first(ghicp_ctx* ctx, const GhRsSort& R, const K* kin, const unsigned* kbase, int bit_begin, unsigned* table) {
+  const size_t words = (size_t)R.S.toff[R.S.nseg] * (size_t)R.first.nd;
+  std::vector<unsigned> left(words), own(words);
+  GH_HIP(hipMemcpyAsync(left.data(), table, words * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(hipStreamSynchronize(ctx->stream));
+  if (R.first.nd == 512) hipLaunchKernelGGL((k_rss_hist<K, 512>), dim3(R.S.toff[R.S.nseg]), dim3(PT), 0, ctx->stream, kin, R.S, kbase, bit_begin, R.first.mask, table);
+  else hipLaunchKernelGGL((k_rss_hist<K, 256>), dim3(R.S.toff[R.S.nseg]), dim3(PT), 0, ctx->stream, kin, R.S, kbase, bit_begin, R.first.mask, table);
+  GH_HIP(hipMemcpyAsync(own.data(), table, words * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->sort_hist_checked++;
+  if (left != own) {
+    ctx->sort_hist_mismatched++;
+    return ctx->fail(GHICP_ERR_INTERNAL, "segmented sort: the first place's counts left by the key kernel differ from the keys' own");
+  }
+  return GHICP_OK;
+}
+
+template <typename K>
+int radix_sort_seg_impl(ghicp_ctx* ctx, const K* kin, K* kout, const unsigned* vin, unsigned* vout, const GhRsSort& R, const unsigned* kbase, int bit_begin) {
+  const GhRsSegs& S = R.S;
+  const GhRsPlan& P = R.P;
+  const int nseg = S.nseg;
+  const long long n = S.off[nseg];
+  if (n <= 0) return GHICP_OK;
+  hipStream_t s = ctx->stream;
+  const bool hasv = vin != nullptr;
+  if (P.places == 0) {
+    GH_HIP(hipMemcpyAsync(kout, kin, (size_t)n * sizeof(K), hipMemcpyDeviceToDevice, s));
+    if (hasv) GH_HIP(hipMemcpyAsync(vout, vin, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+    return GHICP_OK;
+  }
+  const bool wide = rs_wide(P);
+  const unsigned* nov = nullptr;
+  unsigned* novo = nullptr;
+  if (R.longest <= TILE) {
+    if (hasv && wide) hipLaunchKernelGGL((k_rss_small<K, true, 512>), dim3(nseg), dim3(PT), 0, s, kin, vin, kout, vout, S, kbase, bit_begin, P);
+    else if (hasv) hipLaunchKernelGGL((k_rss_small<K, true, 256>), dim3(nseg), dim3(PT), 0, s, kin, vin, kout, vout, S, kbase, bit_begin, P);
+    else if (wide) hipLaunchKernelGGL((k_rss_small<K, false, 512>), dim3(nseg), dim3(PT), 0, s, kin, nov, kout, novo, S, kbase, bit_begin, P);
+    else hipLaunchKernelGGL((k_rss_small<K, false, 256>), dim3(nseg), dim3(PT), 0, s, kin, nov, kout, novo, S, kbase, bit_begin, P);
+    GH_HIP(hipGetLastError());
+    return GHICP_OK;
+  }
+  unsigned *table, *part;
+  GH_TRY(rs_table(ctx, R, &table, &part));
+  const bool have_first = R.have_first && R.first.table == table;  // (a table that moved since gh_rs_seg_begin: the counts are taken again)
+  if (have_first && ctx->sort_hist_check) GH_TRY(rs_check_first<K>(ctx, R, kin, kbase, bit_begin, table));
+  K* spare_k = nullptr;
+  unsigned* spare_v = nullptr;
+  if (P.places > 1) {  // the input is left alone, as in radix_sort_impl
+    char* sp;
+    const size_t kb = (((size_t)n * sizeof(K) + 255) / 256) * 256;
+    GH_TRY(ctx->reserve(B_GRID_TMP, kb + (hasv ? (size_t)n * sizeof(unsigned) : 0) + 16, &sp));
+    spare_k = reinterpret_cast<K*>(sp);
+    spare_v = reinterpret_cast<unsigned*>(sp + kb);
+  }
+  const bool one_chunk = R.longest <= (long long)RC * TILE;
+  const K* src_k = kin;
+  const unsigned* src_v = vin;
+  int shift = bit_begin;
+  for (int p = 0; p < P.places; p++) {
+    const bool to_out = ((P.places - 1 - p) & 1) == 0;
+    K* dst_k = to_out ? kout : spare_k;
+    unsigned* dst_v = to_out ? vout : spare_v;
+    const unsigned mask = (1u << P.width[p]) - 1u;
+    const bool w9 = P.width[p] > 8, first = p == 0 && have_first;
+    if (hasv && w9) rss_place<K, true, 512>(s, src_k, src_v, dst_k, dst_v, S, one_chunk, kbase, shift, mask, table, part, first);
+    else if (hasv) rss_place<K, true, 256>(s, src_k, src_v, dst_k, dst_v, S, one_chunk, kbase, shift, mask, table, part, first);
+    else if (w9) rss_place<K, false, 512>(s, src_k, nov, dst_k, novo, S, one_chunk, kbase, shift, mask, table, part, first);
+    else rss_place<K, false, 256>(s, src_k, nov, dst_k, novo, S, one_chunk, kbase, shift, mask, table, part, first);
+    shift += P.width[p];
+    src_k = dst_k;
+    src_v = dst_v;
+  }
+  GH_HIP(hipGetLastError());
+  return GHICP_OK;
+}
 
 template <int MODE>
 int select_impl(ghicp_ctx* ctx, const void* in, long long n, unsigned* out, int* d_count, const unsigned* vals = nullptr) {
@@ -507,6 +823,31 @@ int gh_radix_sort_u32(ghicp_ctx* ctx, const unsigned* keys_in, unsigned* keys_ou
 int gh_radix_sort_u64(ghicp_ctx* ctx, const unsigned long long* keys_in, unsigned long long* keys_out, const unsigned* vals_in, unsigned* vals_out, long long n,
                       int bit_begin, int bit_end) {
   return radix_sort_impl<unsigned long long>(ctx, keys_in, keys_out, vals_in, vals_out, n, bit_begin, bit_end);
+}
+
+int gh_rs_seg_begin(ghicp_ctx* ctx, int nseg, const int* off, int bits, int max_width, GhRsSort* R) {
+  if (nseg <= 0 || nseg > GH_RS_MAX_SEGS || off[0] != 0) return ctx->fail(GHICP_ERR_ARG, "segmented sort: 1 .. %d segments from offset 0", GH_RS_MAX_SEGS);
+  R->longest = gh_rs_segs_make(&R->S, nseg, off);
+  R->P = gh_rs_plan(bits, max_width ? max_width : ctx->sort_digit_bits);
+  R->first.table = nullptr;
+  R->first.nd = R->P.places && R->P.width[0] > 8 ? 512 : 256;
+  R->first.mask = R->P.places ? (1u << R->P.width[0]) - 1u : 0u;
+  R->have_first = false;
+  if (R->P.places > 0 && R->longest > TILE) {
+    unsigned* part;
+    GH_TRY(rs_table(ctx, *R, &R->first.table, &part));
+  }
+  return GHICP_OK;
+}
+
+int gh_radix_sort_seg_u32(ghicp_ctx* ctx, const unsigned* keys_in, unsigned* keys_out, const unsigned* vals_in, unsigned* vals_out, const GhRsSort& R,
+                          const unsigned* seg_base, int bit_begin) {
+  return radix_sort_seg_impl<unsigned>(ctx, keys_in, keys_out, vals_in, vals_out, R, seg_base, bit_begin);
+}
+
+int gh_radix_sort_seg_u64(ghicp_ctx* ctx, const unsigned long long* keys_in, unsigned long long* keys_out, const unsigned* vals_in, unsigned* vals_out,
+                          const GhRsSort& R, int bit_begin) {
+  return radix_sort_seg_impl<unsigned long long>(ctx, keys_in, keys_out, vals_in, vals_out, R, nullptr, bit_begin);
 }
 
 namespace {
@@ -610,4 +951,64 @@ extern "C" int ghicp_sort_pairs(ghicp_ctx* ctx, int key_bytes, const void* keys_
     GH_TRY(gh_radix_sort_u64(ctx, ki, ko, vi, vo, n, bit_begin, bit_end));
   }
   return sg.finish();
+}
+
+extern "C" int ghicp_sort_segments(ghicp_ctx* ctx, int key_bytes, const void* keys_in, void* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int32_t n_segs,
+                                   const int64_t* seg_off, const uint32_t* seg_base, int bit_begin, int bits, int max_digit_bits) {
+  GH_ENTER(ctx);
+  GH_ARG((key_bytes == 4 || key_bytes == 8) && n_segs >= 1 && n_segs <= GH_RS_MAX_SEGS && seg_off != nullptr && seg_off[0] == 0);
+  GH_ARG(bit_begin >= 0 && bits >= 0 && bit_begin + bits <= 8 * key_bytes && (max_digit_bits == 0 || max_digit_bits == 8 || max_digit_bits == 9));
+  GH_ARG(seg_base == nullptr || key_bytes == 4);
+  int off[GH_RS_MAX_SEGS + 1];
+  for (int s = 0; s <= n_segs; s++) {
+    GH_ARG(seg_off[s] < (1ll << 31) - 2 && (s == 0 || seg_off[s] >= seg_off[s - 1]));
+    off[s] = (int)seg_off[s];
+  }
+  const int64_t n = seg_off[n_segs];
+  GH_ARG((vals_in == nullptr) == (vals_out == nullptr) && (n == 0 || (keys_in != nullptr && keys_out != nullptr && keys_in != keys_out)));
+  if (n == 0) return GHICP_OK;
+  {
+    const size_t kbytes = (size_t)n * (size_t)key_bytes, vbytes = (size_t)n * sizeof(uint32_t);
+    GH_ARG(!ranges_overlap(keys_out, kbytes, keys_in, kbytes) && !ranges_overlap(keys_out, kbytes, vals_in, vbytes) && !ranges_overlap(keys_out, kbytes, vals_out, vbytes));
+    GH_ARG(!ranges_overlap(vals_out, vbytes, vals_in, vbytes) && !ranges_overlap(vals_out, vbytes, keys_in, kbytes));
+  }
+  Stager sg(ctx);
+  const unsigned *vi = nullptr, *sb = nullptr;
+  unsigned* vo = nullptr;
+  if (vals_in) {
+    GH_TRY(sg.in(vals_in, (size_t)n, &vi));
+    GH_TRY(sg.out(vals_out, (size_t)n, &vo));
+  }
+  if (seg_base) GH_TRY(sg.in(seg_base, (size_t)n_segs, &sb));
+  const unsigned *ki4 = nullptr;
+  const unsigned long long* ki8 = nullptr;
+  unsigned* ko4 = nullptr;
+  unsigned long long* ko8 = nullptr;
+  if (key_bytes == 4) {
+    GH_TRY(sg.in(static_cast<const unsigned*>(keys_in), (size_t)n, &ki4));
+    GH_TRY(sg.out(static_cast<unsigned*>(keys_out), (size_t)n, &ko4));
+  } else {
+    GH_TRY(sg.in(static_cast<const unsigned long long*>(keys_in), (size_t)n, &ki8));
+    GH_TRY(sg.out(static_cast<unsigned long long*>(keys_out), (size_t)n, &ko8));
+  }
+  GhRsSort R;
+  GH_TRY(gh_rs_seg_begin(ctx, n_segs, off, bits, max_digit_bits, &R));
+  const int rc = key_bytes == 4 ? gh_radix_sort_seg_u32(ctx, ki4, ko4, vi, vo, R, sb, bit_begin) : gh_radix_sort_seg_u64(ctx, ki8, ko8, vi, vo, R, bit_begin);
+  GH_TRY(rc);
+  return sg.finish();
+}
+
+// test hook: with it on, every segmented sort that is handed the first place's counts by a key-making kernel takes them again from the keys and
+// compares (a host round trip per sort); the two counters say how many sorts were checked and how many differed
+extern "C" int ghicp_ctx_set_sort_hist_check(ghicp_ctx* ctx, int on) {
+  GH_ENTER(ctx);
+  ctx->sort_hist_check = on != 0;
+  return GHICP_OK;
+}
+extern "C" int ghicp_ctx_sort_hist_checks(ghicp_ctx* ctx, int64_t* checked, int64_t* mismatched) {
+  GH_ENTER(ctx);
+  GH_ARG(checked != nullptr && mismatched != nullptr);
+  *checked = ctx->sort_hist_checked;
+  *mismatched = ctx->sort_hist_mismatched;
+  return GHICP_OK;
 }

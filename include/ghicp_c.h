@@ -168,6 +168,18 @@ int ghicp_box_filter(ghicp_ctx* ctx, const float* xyz, int64_t n, int stride, co
  * an input or the other output, even by a partial range, is GHICP_ERR_ARG and nothing is written. */
 int ghicp_sort_pairs(ghicp_ctx* ctx, int key_bytes, const void* keys_in, void* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int64_t n,
                      int bit_begin, int bit_end);
+/* The same sort, segment by segment in one call (the clouds of a batched front end): segment s is the items [seg_off[s], seg_off[s + 1]) of
+ * the arrays, seg_off [host] = n_segs + 1 ascending offsets from 0, 1 <= n_segs <= 64, empty segments allowed; each segment is sorted, stably,
+ * on the bits [bit_begin, bit_begin + bits) of key - seg_base[s].  seg_base (4-byte keys only; n_segs words, like the arrays a device pointer
+ * unless the context stages host pointers) may be NULL for 0; every key of a segment must be >= its base.  max_digit_bits: 8 or 9, the widest
+ * digit of a place (0: the context's default); the digit places are planned from `bits`.  Buffers as for ghicp_sort_pairs. */
+int ghicp_sort_segments(ghicp_ctx* ctx, int key_bytes, const void* keys_in, void* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int32_t n_segs,
+                        const int64_t* seg_off, const uint32_t* seg_base, int bit_begin, int bits, int max_digit_bits);
+/* Test hook of the batched front end's sorts: the kernels that make the voxel and cell keys leave the first digit place's per-tile counts
+ * for the sort.  With the check on, every such sort takes the counts again from the keys and compares (GHICP_ERR_INTERNAL when they differ; a
+ * host round trip per sort).  *checked / *mismatched: sorts compared / found different since the context was created. */
+int ghicp_ctx_set_sort_hist_check(ghicp_ctx* ctx, int on);
+int ghicp_ctx_sort_hist_checks(ghicp_ctx* ctx, int64_t* checked, int64_t* mismatched);
 /* The other device-wide primitives under the front end (prims.hip), as primitives; n < 2^31 - 2 as for the sort, n == 0 is fine.
  * Inclusive prefix sum in place, modulo 2^32: data[i] = data[0] + ... + data[i].  `data` needs the alignment of its type only. */
 int ghicp_scan_inclusive_u32(ghicp_ctx* ctx, uint32_t* data, int64_t n);
