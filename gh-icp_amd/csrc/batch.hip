@@ -31,14 +31,8 @@ namespace {
 
 enum { FB_CLOUD_BY_CLOUD = -1, FB_HALVE = -2 };  // a stage's verdict that the batch as it stands is not covered: the entry point takes the fall-back
 
-__global__ void k_fb_bbox_init(int* __restrict__ bb, int nb) {  // enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3 per cloud
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < nb * 6) bb[i] = (i % 6) < 3 ? 0x7f7fffff : (int)0x80800000;
-}
-
 // per-cloud bounding boxes; which = 0: raw clouds, 1: base = concatenated float4 points (moff), 2: base = float3 candidates (coff)
 __global__ __launch_bounds__(256) void k_fb_bbox(const FbBlock* __restrict__ D, const float* __restrict__ base, int which, int* __restrict__ bb) {
-  __shared__ float smin[3][4], smax[3][4];
   const int b = blockIdx.y;
   const float* xyz;
   long long n;
@@ -54,19 +48,7 @@ __global__ __launch_bounds__(256) void k_fb_bbox(const FbBlock* __restrict__ D, 
   float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     for (int d = 0; d < 3; d++) { const float v = xyz[i * stride + d]; mn[d] = fminf(mn[d], v); mx[d] = fmaxf(mx[d], v); }
-  for (int d = 0; d < 3; d++) {
-    for (int o = 32; o > 0; o >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { smin[d][threadIdx.x >> 6] = mn[d]; smax[d][threadIdx.x >> 6] = mx[d]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    float a = smin[d][0], e = smax[d][0];
-    for (int w = 1; w < 4; w++) { a = fminf(a, smin[d][w]); e = fmaxf(e, smax[d][w]); }
-    auto enc = [](float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; };
-    atomicMin(bb + b * 6 + d, enc(a));
-    atomicMax(bb + b * 6 + 3 + d, enc(e));
-  }
+  gh_box_block(mn, mx, bb + b * 6);
 }
 
 // filter.hpp:57-70 per cloud; the cloud id sits above the voxel key's bits
@@ -174,24 +156,13 @@ __global__ __launch_bounds__(256) void k_fb_cell_keys(const FbBlock* __restrict_
     if (j < t.here) {
       const int i = t.first + j;
       const float4 P = dsg[i];
-      const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
-      const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
-      const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
-      const unsigned cell = ((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz;
+      const unsigned cell = gh_cell_key(g, P.x, P.y, P.z);
       keys[i] = cb + cell;
       vals[i] = (unsigned)i;
       if (hist) gh_rs_first_add(cnt, cell & F.mask);
     }
   }
   if (hist) gh_rs_first_store(cnt, F, (int)blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void k_fb_gather_sorted(const float4* __restrict__ dsg, const unsigned* __restrict__ vals, int M, float4* __restrict__ pts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
-  const unsigned s = vals[i];
-  const float4 P = dsg[s];
-  pts[i] = make_float4(P.x, P.y, P.z, __uint_as_float(s));  // w = index into the concatenated cloud
 }
 
 // pca.hip:k_pca_cells over the occupied cells of all clouds of the batch
@@ -308,25 +279,12 @@ __global__ __launch_bounds__(BT) void k_fb_bsc(const FbBlock* __restrict__ D, co
   gh_bsc_keypoint(G, C, q - D->koff[b], D->koff[b + 1] - D->koff[b], D->c[b].feat, lcs + (size_t)D->koff[b] * 12);
 }
 
-void decode_box(const int* enc, float* mm) {
-  for (int k = 0; k < 6; k++) {
-    const int i = enc[k] >= 0 ? enc[k] : enc[k] ^ 0x7fffffff;
-    memcpy(&mm[k], &i, 4);
-  }
-}
-
 // one grid of the batch: global cell keys -> stable sort -> points in cell order -> cell table
 int build_grid(ghicp_ctx* ctx, const FbBlock* D, const FbBlock* H, int which, const float4* dsg, int M, unsigned total_cells, const GridSlots& sl,
                const float4** pts_out, const unsigned** start_out, const unsigned** keys_out) {
   hipStream_t s = ctx->stream;
-  unsigned *keys, *keys2, *vals, *vals2, *start;
-  float4* pts;
-  GH_TRY(ctx->reserve(sl.keys, (size_t)M + 1, &keys));
-  GH_TRY(ctx->reserve(sl.keys2, (size_t)M + 1, &keys2));
-  GH_TRY(ctx->reserve(sl.vals, (size_t)M + 1, &vals));
-  GH_TRY(ctx->reserve(sl.vals2, (size_t)M + 1, &vals2));
-  GH_TRY(ctx->reserve(sl.start, (size_t)total_cells + 2, &start));
-  GH_TRY(ctx->reserve(sl.pts, (size_t)M + 1, &pts));
+  GridBufs B;
+  GH_TRY(gh_grid_reserve(ctx, sl, (size_t)M, total_cells, true, &B));
   hipEvent_t kg = ctx->kt_begin(KT_FB_GRID);
   // stable: a cell keeps its points in down-sampled order (prims.hip).  The down-sampled clouds are the sort's segments: a cloud's points are
   // sorted on the cell inside the cloud's own grid (key - cell base), so the bits are those of the largest grid, not of all grids together.
@@ -340,15 +298,15 @@ int build_grid(ghicp_ctx* ctx, const FbBlock* D, const FbBlock* H, int which, co
   GH_TRY(gh_rs_seg_begin(ctx, H->nb, H->moff, cell_bits, 0, &R));
   if (ctx->sort_trace) fprintf(stderr, "sort_trace grid%d clouds=%d keys=%d bits_one_grid=%d bits_all_grids=%d places=%d\n", which + 1, H->nb, M, cell_bits, bits_for(total_cells), R.P.places);
   if (!ctx->sort_segments) R.first.table = nullptr;
-  hipLaunchKernelGGL(k_fb_cell_keys, dim3(R.S.toff[R.S.nseg]), dim3(256), 0, s, D, which, dsg, R.S, keys, vals, R.first);
+  hipLaunchKernelGGL(k_fb_cell_keys, dim3(R.S.toff[R.S.nseg]), dim3(256), 0, s, D, which, dsg, R.S, B.keys, B.vals, R.first);
   R.have_first = R.first.table != nullptr;
-  if (ctx->sort_segments) GH_TRY(gh_radix_sort_seg_u32(ctx, keys, keys2, vals, vals2, R, which ? D->cb2 : D->cb1, 0));
-  else GH_TRY(gh_radix_sort_u32(ctx, keys, keys2, vals, vals2, M, 0, bits_for(total_cells)));
-  hipLaunchKernelGGL(k_fb_gather_sorted, dim3(cdiv(M, 256)), dim3(256), 0, s, dsg, vals2, M, pts);
-  gh_cell_start_launch(s, keys2, (unsigned)M, total_cells, start);  // (round 5: the table is filled from the sorted keys, grid.hip)
+  if (ctx->sort_segments) GH_TRY(gh_radix_sort_seg_u32(ctx, B.keys, B.keys2, B.vals, B.vals2, R, which ? D->cb2 : D->cb1, 0));
+  else GH_TRY(gh_radix_sort_u32(ctx, B.keys, B.keys2, B.vals, B.vals2, M, 0, bits_for(total_cells)));
+  hipLaunchKernelGGL(k_gather_sorted_f4, dim3(cdiv(M, 256)), dim3(256), 0, s, dsg, (const unsigned*)B.vals2, M, B.pts);  // w = index into the concatenated cloud
+  gh_cell_start_launch(s, B.keys2, (unsigned)M, total_cells, B.start);  // (round 5: the table is filled from the sorted keys, grid.hip)
   ctx->kt_end(KT_FB_GRID, kg);
   GH_HIP(hipGetLastError());
-  *pts_out = pts; *start_out = start; *keys_out = keys2;
+  *pts_out = B.pts; *start_out = B.start; *keys_out = B.keys2;
   return GHICP_OK;
 }
 
@@ -397,7 +355,7 @@ int FbRun::begin(const float* const* xyz, const int64_t* n, int stride) {
 // ------------------------------------------------------------------ boxes of the raw clouds, voxel multipliers          (sync 1)
 int FbRun::raw_boxes() {
   GH_HIP(upload());
-  hipLaunchKernelGGL(k_fb_bbox_init, dim3(cdiv(nb * 6, 256)), dim3(256), 0, s, O->bb, nb);
+  hipLaunchKernelGGL(k_box_init, dim3(cdiv(nb * 6, 256)), dim3(256), 0, s, O->bb, nb * 6);
   hipLaunchKernelGGL(k_fb_bbox, dim3(64, nb), dim3(256), 0, s, (const FbBlock*)D, (const float*)nullptr, 0, O->bb);
   GH_HIP(report());
   ebmax = 1;
@@ -405,7 +363,7 @@ int FbRun::raw_boxes() {
     FbCloud& C = H->c[b];
     if (C.n == 0) continue;
     float mm[6];
-    decode_box(HO->bb + b * 6, mm);
+    gh_box_decode(HO->bb + b * 6, mm);
     C.vinv = 1.0f / cfg.voxel;  // filter.hpp:30
     unsigned long long maxv[3];
     for (int d = 0; d < 3; d++) {
@@ -466,7 +424,7 @@ int FbRun::voxel() {
   hipLaunchKernelGGL(k_fb_voxel_bounds, dim3(1), dim3(128), 0, s, headpos, misc, D, O);
   hipLaunchKernelGGL(k_fb_gather_ds, dim3(cdiv(N + nb, 256)), dim3(256), 0, s, (const FbBlock*)D, headpos, vvals2,
                      idx_bits > 0 ? (const unsigned long long*)vkeys2 : (const unsigned long long*)nullptr, idx_bits > 0 ? (1ull << idx_bits) - 1ull : 0ull, dsg);
-  hipLaunchKernelGGL(k_fb_bbox_init, dim3(cdiv(nb * 6, 256)), dim3(256), 0, s, O->bb, nb);
+  hipLaunchKernelGGL(k_box_init, dim3(cdiv(nb * 6, 256)), dim3(256), 0, s, O->bb, nb * 6);
   hipLaunchKernelGGL(k_fb_bbox, dim3(64, nb), dim3(256), 0, s, (const FbBlock*)D, reinterpret_cast<const float*>(dsg), 1, O->bb);
   ctx->kt_end(KT_FB_VOXEL, kv1);
   GH_HIP(hipGetLastError());
@@ -486,7 +444,7 @@ int FbRun::plan_grids(BscConst* BC) {
     ghicp_cloud* c = clouds[b];
     c->m = H->moff[b + 1] - H->moff[b];
     float mm[6] = {0, 0, 0, 0, 0, 0};
-    if (c->m > 0) decode_box(HO->bb + b * 6, mm);
+    if (c->m > 0) gh_box_decode(HO->bb + b * 6, mm);
     c->bbx = (float)((double)mm[3] - (double)mm[0] + (double)mm[4] - (double)mm[1] + (double)mm[5] - (double)mm[2]);  // main:91-93
     H->g1[b] = gh_grid_desc(mm, c->m, r_pca * 1.0001f);
     H->cb1[b] = (unsigned)t1;

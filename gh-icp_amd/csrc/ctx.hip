@@ -1,6 +1,7 @@
 // Context management + small stand-alone entry points (rigid solve, cloud transform, gather, bbox).
 #include "ctx.h"
 #include "devmath.h"
+#include "grid.h"
 
 extern "C" const char* ghicp_version(void) { return "ghicp-hip 0.1 (gfx950)"; }
 
@@ -290,32 +291,14 @@ __global__ __launch_bounds__(256) void k_gather4(const float* __restrict__ xyz, 
   out[i] = make_float4(xyz[s * stride], xyz[s * stride + 1], xyz[s * stride + 2], 0.f);
 }
 
-__global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ xyz, long long n, int stride, float* __restrict__ mm /*6: min xyz, max xyz as ordered ints*/) {
-  __shared__ float smin[3][4], smax[3][4];
+__global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ xyz, long long n, int stride, int* __restrict__ box /*6: min xyz, max xyz as ordered ints*/) {
   float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     for (int d = 0; d < 3; d++) { const float v = xyz[i * stride + d]; mn[d] = fminf(mn[d], v); mx[d] = fmaxf(mx[d], v); }
-  for (int d = 0; d < 3; d++) {
-    for (int o = 32; o > 0; o >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { smin[d][threadIdx.x >> 6] = mn[d]; smax[d][threadIdx.x >> 6] = mx[d]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    float a = smin[d][0], b = smax[d][0];
-    for (int w = 1; w < 4; w++) { a = fminf(a, smin[d][w]); b = fmaxf(b, smax[d][w]); }
-    // float atomic min/max through the order-preserving int mapping
-    auto enc = [](float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; };
-    atomicMin(reinterpret_cast<int*>(mm) + d, enc(a));
-    atomicMax(reinterpret_cast<int*>(mm) + 3 + d, enc(b));
-  }
+  gh_box_block(mn, mx, box);
 }
 
 }  // namespace
-
-__global__ void k_bbox_init(int* mm) {  // enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3
-  if (threadIdx.x < 6) mm[threadIdx.x] = threadIdx.x < 3 ? 0x7f7fffff : (int)0x80800000;
-}
 
 // Bounding box of a device cloud on the host.  Small transfers go through the context's PINNED scratch: a pageable hipMemcpyAsync is
 // staged and serialised inside the runtime (the front end did 12 of them per cloud from 16 threads).  The box of the cloud a front end
@@ -327,15 +310,12 @@ int gh_bbox_dev(ghicp_ctx* ctx, const float* xyz, long long n, int stride, float
   }
   int* d;
   GH_TRY(ctx->reserve(B_GRID_MISC, 64, &d));
-  hipLaunchKernelGGL(k_bbox_init, dim3(1), dim3(64), 0, ctx->stream, d);
-  if (n > 0) hipLaunchKernelGGL(k_bbox, dim3(min(cdiv(n, 256), 2048)), dim3(256), 0, ctx->stream, xyz, n, stride, reinterpret_cast<float*>(d));
+  hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d, 6);
+  if (n > 0) hipLaunchKernelGGL(k_bbox, dim3(min(cdiv(n, 256), 2048)), dim3(256), 0, ctx->stream, xyz, n, stride, d);
   int* h = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->pinned) + 256);
   GH_HIP(hipMemcpyAsync(h, d, 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   GH_HIP(hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < 6; k++) {
-    int i = h[k] >= 0 ? h[k] : h[k] ^ 0x7fffffff;
-    memcpy(&mm_host6[k], &i, 4);
-  }
+  gh_box_decode(h, mm_host6);
   return GHICP_OK;
 }
 

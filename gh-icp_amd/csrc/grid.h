@@ -66,6 +66,12 @@ inline int bits_for(unsigned long long maxv) {  // bits of a radix sort over key
 struct GridSlots {
   BufSlot keys, keys2, vals, vals2, start, pts;
 };
+// the buffers of one grid build in a GridSlots set: n + 1 keys / vals (and points, when want_pts), cells + 2 cell starts; grid.hip
+struct GridBufs {
+  unsigned *keys, *keys2, *vals, *vals2, *start;
+  float4* pts;
+};
+int gh_grid_reserve(ghicp_ctx* ctx, const GridSlots& slots, size_t n, size_t cells, bool want_pts, GridBufs* out);
 
 // Builds a grid with `cell` >= search radius over xyz (device, n x stride floats). Synchronises once
 // (bounding box -> host) to size the cell table.
@@ -78,6 +84,52 @@ __device__ inline int gh_cell_coord(float v, float mn, float inv, int dim) {
   int c = (int)floorf((v - mn) * inv);
   return min(max(c, 0), dim - 1);
 }
+// linear key of the point's cell, z fastest; a batch adds the cell base of the point's cloud or pair
+__device__ inline unsigned gh_cell_key(const GridDesc& g, float x, float y, float z) {
+  const int cx = gh_cell_coord(x, g.mn[0], g.inv, g.dim[0]);
+  const int cy = gh_cell_coord(y, g.mn[1], g.inv, g.dim[1]);
+  const int cz = gh_cell_coord(z, g.mn[2], g.inv, g.dim[2]);
+  return ((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz;
+}
+
+// ---- bounding boxes on the device: 6 ints per box, min xyz then max xyz, each a float through the order-preserving float -> int mapping,
+// so that atomicMin / atomicMax on the ints reduce the floats exactly (no float atomics)
+__host__ __device__ inline int gh_ord_enc(float f) {
+  int i;
+  memcpy(&i, &f, 4);
+  return i >= 0 ? i : i ^ 0x7fffffff;
+}
+__host__ __device__ inline float gh_ord_dec(int e) {
+  const int i = e >= 0 ? e : e ^ 0x7fffffff;
+  float f;
+  memcpy(&f, &i, 4);
+  return f;
+}
+inline void gh_box_decode(const int* enc6, float* mm6) {
+  for (int k = 0; k < 6; k++) mm6[k] = gh_ord_dec(enc6[k]);
+}
+// box[0 .. n6) = enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3 per box: the state every reduction below starts from; grid.hip
+__global__ void k_box_init(int* box, int n6);
+// Block tail of a box reduction, for a 256-thread workgroup: every thread brings the min / max of the points it loaded (+-3.0e38f where it
+// loaded none); wave ladder, the four waves through LDS, then three lanes fold the block's box into box6.  There is a barrier inside: the
+// whole workgroup calls it, so a kernel's early returns come before it and are uniform per workgroup.
+__device__ inline void gh_box_block(float (&mn)[3], float (&mx)[3], int* box6) {
+  __shared__ float smin[3][4], smax[3][4];
+  for (int d = 0; d < 3; d++) {
+    for (int o = 32; o > 0; o >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
+    if ((threadIdx.x & 63) == 0) { smin[d][threadIdx.x >> 6] = mn[d]; smax[d][threadIdx.x >> 6] = mx[d]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int d = threadIdx.x;
+    float a = smin[d][0], b = smax[d][0];
+    for (int w = 1; w < 4; w++) { a = fminf(a, smin[d][w]); b = fmaxf(b, smax[d][w]); }
+    atomicMin(box6 + d, gh_ord_enc(a));
+    atomicMax(box6 + 3 + d, gh_ord_enc(b));
+  }
+}
+// pts[i] = (src[vals[i]].xyz, w = vals[i]): a concatenated cloud in the cell order of its sorted values; grid.hip
+__global__ void k_gather_sorted_f4(const float4* src, const unsigned* vals, int n, float4* pts);
 
 // Enumerates the 9 contiguous candidate runs around cell (cx,cy,cz): calls f(begin, end) for each.
 template <typename F>

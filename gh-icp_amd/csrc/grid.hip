@@ -13,10 +13,7 @@ __global__ __launch_bounds__(256) void k_cell_keys(const float* __restrict__ xyz
                                                    unsigned* __restrict__ vals) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
-  const int cx = gh_cell_coord(xyz[i * stride], g.mn[0], g.inv, g.dim[0]);
-  const int cy = gh_cell_coord(xyz[i * stride + 1], g.mn[1], g.inv, g.dim[1]);
-  const int cz = gh_cell_coord(xyz[i * stride + 2], g.mn[2], g.inv, g.dim[2]);
-  keys[i] = ((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz;
+  keys[i] = gh_cell_key(g, xyz[i * stride], xyz[i * stride + 1], xyz[i * stride + 2]);
   vals[i] = (unsigned)i;
 }
 
@@ -80,6 +77,30 @@ __global__ __launch_bounds__(256) void k_gather_sorted(const float* __restrict__
 
 }  // namespace
 
+__global__ __launch_bounds__(256) void k_box_init(int* box, int n6) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n6) box[i] = (i % 6) < 3 ? 0x7f7fffff : (int)0x80800000;
+}
+
+__global__ __launch_bounds__(256) void k_gather_sorted_f4(const float4* __restrict__ src, const unsigned* __restrict__ vals, int n, float4* __restrict__ pts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned s = vals[i];
+  const float4 P = src[s];
+  pts[i] = make_float4(P.x, P.y, P.z, __uint_as_float(s));
+}
+
+int gh_grid_reserve(ghicp_ctx* ctx, const GridSlots& sl, size_t n, size_t cells, bool want_pts, GridBufs* out) {
+  GH_TRY(ctx->reserve(sl.keys, n + 1, &out->keys));
+  GH_TRY(ctx->reserve(sl.keys2, n + 1, &out->keys2));
+  GH_TRY(ctx->reserve(sl.vals, n + 1, &out->vals));
+  GH_TRY(ctx->reserve(sl.vals2, n + 1, &out->vals2));
+  GH_TRY(ctx->reserve(sl.start, cells + 2, &out->start));
+  out->pts = nullptr;
+  if (want_pts) GH_TRY(ctx->reserve(sl.pts, n + 1, &out->pts));
+  return GHICP_OK;
+}
+
 void gh_cell_start_launch(hipStream_t s, const unsigned* keys, unsigned n, unsigned ncell, unsigned* start) {
   if (n > 0) hipLaunchKernelGGL(k_cell_start_fill, dim3(cdiv(n, 256)), dim3(256), 0, s, keys, n, start);
   hipLaunchKernelGGL(k_cell_start_tail, dim3((unsigned)std::min<long long>(2048, cdiv((long long)ncell + 1, 256))), dim3(256), 0, s, keys, n, ncell, start);
@@ -90,25 +111,19 @@ int gh_grid_build(ghicp_ctx* ctx, const float* xyz, long long n, int stride, flo
   float mm[6] = {0, 0, 0, 0, 0, 0};
   if (n > 0) GH_TRY(gh_bbox_dev(ctx, xyz, n, stride, mm));
   const GridDesc g = gh_grid_desc(mm, n, cell);
-  unsigned *keys, *keys2, *vals, *vals2, *start;
-  float4* pts;
-  GH_TRY(ctx->reserve(sl.keys, (size_t)n + 1, &keys));
-  GH_TRY(ctx->reserve(sl.keys2, (size_t)n + 1, &keys2));
-  GH_TRY(ctx->reserve(sl.vals, (size_t)n + 1, &vals));
-  GH_TRY(ctx->reserve(sl.vals2, (size_t)n + 1, &vals2));
-  GH_TRY(ctx->reserve(sl.start, (size_t)g.ncell + 2, &start));
-  GH_TRY(ctx->reserve(sl.pts, (size_t)n + 1, &pts));
+  GridBufs b;
+  GH_TRY(gh_grid_reserve(ctx, sl, (size_t)n, g.ncell, true, &b));
   if (n > 0) {
-    hipLaunchKernelGGL(k_cell_keys, dim3(cdiv(n, 256)), dim3(256), 0, s, xyz, n, stride, g, keys, vals);
-    GH_TRY(gh_radix_sort_u32(ctx, keys, keys2, vals, vals2, n, 0, bits_for(g.ncell)));  // stable: a cell keeps its points in input order (prims.hip)
-    hipLaunchKernelGGL(k_gather_sorted, dim3(cdiv(n, 256)), dim3(256), 0, s, xyz, stride, vals2, n, pts);
+    hipLaunchKernelGGL(k_cell_keys, dim3(cdiv(n, 256)), dim3(256), 0, s, xyz, n, stride, g, b.keys, b.vals);
+    GH_TRY(gh_radix_sort_u32(ctx, b.keys, b.keys2, b.vals, b.vals2, n, 0, bits_for(g.ncell)));  // stable: a cell keeps its points in input order (prims.hip)
+    hipLaunchKernelGGL(k_gather_sorted, dim3(cdiv(n, 256)), dim3(256), 0, s, xyz, stride, b.vals2, n, b.pts);
   }
-  gh_cell_start_launch(s, keys2, (unsigned)n, g.ncell, start);
+  gh_cell_start_launch(s, b.keys2, (unsigned)n, g.ncell, b.start);
   GH_HIP(hipGetLastError());
   out->d = g;
-  out->pts = pts;
-  out->start = start;
-  out->keys = keys2;
+  out->pts = b.pts;
+  out->start = b.start;
+  out->keys = b.keys2;
   return GHICP_OK;
 }
 

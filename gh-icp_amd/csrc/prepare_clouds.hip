@@ -45,14 +45,8 @@ struct PpTab {
   double* cov[PP_MAX_CLOUDS];
 };
 
-__global__ __launch_bounds__(256) void k_pp_bbox_init(int* __restrict__ bb, int n6) {  // enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3 per cloud
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n6) bb[i] = (i % 6) < 3 ? 0x7f7fffff : (int)0x80800000;
-}
-
 // boxes of the handles' down-sampled clouds (ctx.hip k_bbox per cloud: blockIdx.y + base is the cloud)
 __global__ __launch_bounds__(256) void k_pp_bbox(const float4* const* __restrict__ ds, const int* __restrict__ m, int base, int* __restrict__ bb) {
-  __shared__ float smin[3][4], smax[3][4];
   const int b = base + blockIdx.y;
   const float4* __restrict__ p = ds[b];
   const int n = m[b];
@@ -63,19 +57,7 @@ __global__ __launch_bounds__(256) void k_pp_bbox(const float4* const* __restrict
     mn[1] = fminf(mn[1], P.y); mx[1] = fmaxf(mx[1], P.y);
     mn[2] = fminf(mn[2], P.z); mx[2] = fmaxf(mx[2], P.z);
   }
-  for (int d = 0; d < 3; d++) {
-    for (int o = 32; o > 0; o >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { smin[d][threadIdx.x >> 6] = mn[d]; smax[d][threadIdx.x >> 6] = mx[d]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    float a = smin[d][0], e = smax[d][0];
-    for (int w = 1; w < 4; w++) { a = fminf(a, smin[d][w]); e = fmaxf(e, smax[d][w]); }
-    auto enc = [](float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; };
-    atomicMin(bb + (size_t)b * 6 + d, enc(a));
-    atomicMax(bb + (size_t)b * 6 + 3 + d, enc(e));
-  }
+  gh_box_block(mn, mx, bb + (size_t)b * 6);
 }
 
 // the pass's clouds out of the handles into one array
@@ -94,10 +76,7 @@ __global__ __launch_bounds__(256) void k_pp_cell_keys(const PpTab* __restrict__ 
   const int j = fb_find(T->off, T->nb, i);
   const GridDesc& g = T->g[j];
   const float4 Q = cat[T->src[j] + (i - T->off[j])];
-  const int cx = gh_cell_coord(Q.x, g.mn[0], g.inv, g.dim[0]);
-  const int cy = gh_cell_coord(Q.y, g.mn[1], g.inv, g.dim[1]);
-  const int cz = gh_cell_coord(Q.z, g.mn[2], g.inv, g.dim[2]);
-  keys[i] = T->cb[j] + (((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz);
+  keys[i] = T->cb[j] + gh_cell_key(g, Q.x, Q.y, Q.z);
   vals[i] = (unsigned)i;
 }
 
@@ -129,15 +108,6 @@ __global__ __launch_bounds__(256) void k_pp_scatter(const PpTab* __restrict__ T,
     const unsigned c = e - T->tb[w];
     T->start[w][c] = gstart[T->cb[w] + c] - (unsigned)T->soff[w];
   }
-}
-
-// the k-NN grid's points stay in the context: w = index into the pass's concatenation (batch.hip k_fb_gather_sorted)
-__global__ __launch_bounds__(256) void k_pp_gather_sorted(const float4* __restrict__ cat, const unsigned* __restrict__ vals, int P, float4* __restrict__ pts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  const unsigned s = vals[i];
-  const float4 Q = cat[s];
-  pts[i] = make_float4(Q.x, Q.y, Q.z, __uint_as_float(s));
 }
 
 // rows of the k-NN pass into the handles that asked for them
@@ -230,18 +200,14 @@ struct PpRun {
     }
     H->cb[nb] = (unsigned)cells;
     const int P = H->off[nb];
-    unsigned *keys, *keys2, *vals, *vals2, *start;
-    GH_TRY(ctx->reserve(sl.keys, (size_t)P + 1, &keys));
-    GH_TRY(ctx->reserve(sl.keys2, (size_t)P + 1, &keys2));
-    GH_TRY(ctx->reserve(sl.vals, (size_t)P + 1, &vals));
-    GH_TRY(ctx->reserve(sl.vals2, (size_t)P + 1, &vals2));
-    GH_TRY(ctx->reserve(sl.start, (size_t)cells + 2, &start));
+    GridBufs B;
+    GH_TRY(gh_grid_reserve(ctx, sl, (size_t)P, (size_t)cells, false, &B));  // the points go to the handles (scatter) or to the k-NN pass's own buffer
     GH_TRY(upload(H, D));
-    hipLaunchKernelGGL(k_pp_cell_keys, dim3(cdiv(P, 256)), dim3(256), 0, s, (const PpTab*)D, cat, P, keys, vals);
-    GH_TRY(gh_radix_sort_u32(ctx, keys, keys2, vals, vals2, P, 0, bits_for(cells)));  // stable: a cell keeps its points in down-sampled order (prims.hip)
-    gh_cell_start_launch(s, keys2, (unsigned)P, (unsigned)cells, start);
+    hipLaunchKernelGGL(k_pp_cell_keys, dim3(cdiv(P, 256)), dim3(256), 0, s, (const PpTab*)D, cat, P, B.keys, B.vals);
+    GH_TRY(gh_radix_sort_u32(ctx, B.keys, B.keys2, B.vals, B.vals2, P, 0, bits_for(cells)));  // stable: a cell keeps its points in down-sampled order (prims.hip)
+    gh_cell_start_launch(s, B.keys2, (unsigned)P, (unsigned)cells, B.start);
     GH_HIP(hipGetLastError());
-    out->H = *H; out->D = D; out->P = P; out->cells = (unsigned)cells; out->keys = keys2; out->vals = vals2; out->start = start;
+    out->H = *H; out->D = D; out->P = P; out->cells = (unsigned)cells; out->keys = B.keys2; out->vals = B.vals2; out->start = B.start;
     return GHICP_OK;
   }
 
@@ -290,7 +256,7 @@ int PpRun::boxes(std::vector<PpCloud>& W) {
   GH_TRY(ctx->reserve(B_PP_BOX, bytes + n * 6 * sizeof(int) + 64, &d));
   int* bb = reinterpret_cast<int*>(d + ((bytes + 15) & ~(size_t)15));
   GH_TRY(ctx->upload_table(host.data(), bytes, d));
-  hipLaunchKernelGGL(k_pp_bbox_init, dim3(cdiv((long long)n * 6, 256)), dim3(256), 0, s, bb, (int)(n * 6));
+  hipLaunchKernelGGL(k_box_init, dim3(cdiv((long long)n * 6, 256)), dim3(256), 0, s, bb, (int)(n * 6));
   const int bx = std::min(cdiv(maxm, 256), 64);
   for (size_t base = 0; base < n; base += 32768) {
     const unsigned ny = (unsigned)std::min<size_t>(32768, n - base);
@@ -303,10 +269,7 @@ int PpRun::boxes(std::vector<PpCloud>& W) {
   GH_TRY(wait());
   for (size_t i = 0; i < n; i++) {
     PpCloud& C = W[i];
-    for (int k = 0; k < 6; k++) {
-      const int v = enc[i * 6 + k] >= 0 ? enc[i * 6 + k] : enc[i * 6 + k] ^ 0x7fffffff;
-      memcpy(&C.mm[k], &v, 4);
-    }
+    gh_box_decode(enc.data() + i * 6, C.mm);
     const float* mm = C.mm;
     memset(&C.fine0, 0, sizeof(GridDesc)); memset(&C.knn, 0, sizeof(GridDesc)); memset(&C.ovg, 0, sizeof(GridDesc));
     if (C.grids) {  // the start cell of icp.hip build_index
@@ -445,7 +408,7 @@ int PpRun::knn_pass(PpCloud* W, int nb, int k, bool want_n, bool want_c, const f
   GH_TRY(build(W, who, gd, catk, srcoff, kSlotsB, &B));
   float4* pts;
   GH_TRY(ctx->reserve(B_GRID2_PTS, (size_t)P + 1, &pts));
-  hipLaunchKernelGGL(k_pp_gather_sorted, dim3(cdiv(P, 256)), dim3(256), 0, s, catk, B.vals, P, pts);
+  hipLaunchKernelGGL(k_gather_sorted_f4, dim3(cdiv(P, 256)), dim3(256), 0, s, catk, B.vals, P, pts);  // w = index into the pass's concatenation
   float* nrm = nullptr;
   double* cov = nullptr;
   if (want_n) GH_TRY(ctx->reserve(B_PP_NRM, (size_t)P * 3 + 3, &nrm));

@@ -10,8 +10,8 @@
 // as in k_reciprocal.
 //
 // Per iteration (gh_refine_recip_step), after the forward search:
-//   k_rr_box_init, k_rr_box   per-pair bounding box of the pair's slice of cur: 2-D launch, wave shuffles, then 4 waves through LDS, then six
-//                             ordered-int atomicMin / atomicMax per block
+//   k_box_init, k_rr_box      per-pair bounding box of the pair's slice of cur: 2-D launch, then the block tail every box reduction shares
+//                             (gh_box_block, grid.h: wave shuffles, 4 waves through LDS, six ordered-int atomicMin / atomicMax per block)
 //   k_rr_plan                 one thread per pair: its fine grid (from the target's fine cell) and its coarse grid (8 x the fine cell that came
 //                             out) inside the pair's ranges of the table -- gh_recip_grid (refine_recip_plan.h: the budget rule is written there)
 //   k_rr_keys                 every point twice: key = base_f[p] + fine cell in the first half, base_c[p] + coarse cell in the second
@@ -35,23 +35,11 @@ namespace {
 using namespace icpdev;
 using namespace rfdev;
 
-__global__ __launch_bounds__(256) void k_rr_box_init(int* box, int n6) {  // enc(+FLT_MAX) x 3, enc(-FLT_MAX) x 3 per pair
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < n6) box[t] = t % 6 < 3 ? 0x7f7fffff : (int)0x80800000;
-}
-
-__device__ inline int ord_enc(float f) {  // order-preserving float -> int (k_bbox, ctx.hip)
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ inline float ord_dec(int e) { return __int_as_float(e >= 0 ? e : e ^ 0x7fffffff); }
-
 __global__ __launch_bounds__(256) void k_rr_box(RefineArgs A, RecipStage R) {
   const unsigned p = blockIdx.y;
   const RefinePair& D = A.pair[p];
   if (blockIdx.x * 256u >= (unsigned)D.ns) return;
   if (frozen(&A.st[p])) return;
-  __shared__ float smin[3][4], smax[3][4];
   const float4* cur = A.cur + D.off;
   float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < D.ns; i += gridDim.x * 256) {
@@ -60,18 +48,7 @@ __global__ __launch_bounds__(256) void k_rr_box(RefineArgs A, RecipStage R) {
     mn[1] = fminf(mn[1], P.y); mx[1] = fmaxf(mx[1], P.y);
     mn[2] = fminf(mn[2], P.z); mx[2] = fmaxf(mx[2], P.z);
   }
-  for (int d = 0; d < 3; d++) {
-    for (int o = 32; o > 0; o >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { smin[d][threadIdx.x >> 6] = mn[d]; smax[d][threadIdx.x >> 6] = mx[d]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    float a = smin[d][0], b = smax[d][0];
-    for (int w = 1; w < 4; w++) { a = fminf(a, smin[d][w]); b = fmaxf(b, smax[d][w]); }
-    atomicMin(&R.box[p * 6 + d], ord_enc(a));
-    atomicMax(&R.box[p * 6 + 3 + d], ord_enc(b));
-  }
+  gh_box_block(mn, mx, R.box + p * 6);
 }
 
 __device__ inline GridDesc desc_of(const RecipGrid& g, int n) {
@@ -87,19 +64,12 @@ __global__ __launch_bounds__(64) void k_rr_plan(RefineArgs A, RecipStage R, int 
   const int p = blockIdx.x * 64 + threadIdx.x;
   if (p >= np || frozen(&A.st[p])) return;
   float mm[6];
-  for (int k = 0; k < 6; k++) mm[k] = ord_dec(R.box[p * 6 + k]);
+  for (int k = 0; k < 6; k++) mm[k] = gh_ord_dec(R.box[p * 6 + k]);
   const RecipRange rg = R.range[p];
   const RecipGrid gf = gh_recip_grid(mm, A.pair[p].X.fine.cell, rg.cells_f);  // ghicp_icp: the target's fine cell ...
   const RecipGrid gc = gh_recip_grid(mm, (1.0f / gf.inv) * 8.0f, rg.cells_c);   // ... and 8 x the fine cell that was used
   R.grid[2 * p] = desc_of(gf, A.pair[p].ns);
   R.grid[2 * p + 1] = desc_of(gc, A.pair[p].ns);
-}
-
-__device__ inline unsigned cell_key(const GridDesc& g, const float4& P) {
-  const int cx = gh_cell_coord(P.x, g.mn[0], g.inv, g.dim[0]);
-  const int cy = gh_cell_coord(P.y, g.mn[1], g.inv, g.dim[1]);
-  const int cz = gh_cell_coord(P.z, g.mn[2], g.inv, g.dim[2]);
-  return ((unsigned)cx * g.dim[1] + cy) * g.dim[2] + cz;
 }
 
 __global__ __launch_bounds__(256) void k_rr_keys(RefineArgs A, RecipStage R) {
@@ -113,8 +83,8 @@ __global__ __launch_bounds__(256) void k_rr_keys(RefineArgs A, RecipStage R) {
   unsigned kf = rg.base_f, kc = rg.base_c;  // a frozen pair: the first cell of its own ranges
   if (!frozen(&A.st[p])) {
     const float4 P = A.cur[gi];
-    kf += cell_key(R.grid[2 * p], P);
-    kc += cell_key(R.grid[2 * p + 1], P);
+    kf += gh_cell_key(R.grid[2 * p], P.x, P.y, P.z);
+    kc += gh_cell_key(R.grid[2 * p + 1], P.x, P.y, P.z);
   }
   R.keys[gi] = kf;
   R.keys[R.npts + gi] = kc;
@@ -195,12 +165,10 @@ int gh_refine_recip_begin(ghicp_ctx* ctx, const RefinePair* hd, int np, long lon
   R->box = reinterpret_cast<int*>(desc + b_range);
   R->grid = reinterpret_cast<GridDesc*>(desc + b_range + b_box);
   R->pendc2 = reinterpret_cast<unsigned*>(desc + b_range + b_box + b_grid);
-  GH_TRY(ctx->reserve(B_GRID2_KEYS, (size_t)npts * 2 + 1, &R->keys));
-  GH_TRY(ctx->reserve(B_GRID2_KEYS2, (size_t)npts * 2 + 1, &R->keys2));
-  GH_TRY(ctx->reserve(B_GRID2_VALS, (size_t)npts * 2 + 1, &R->vals));
-  GH_TRY(ctx->reserve(B_GRID2_VALS2, (size_t)npts * 2 + 1, &R->vals2));
-  GH_TRY(ctx->reserve(B_GRID2_PTS, (size_t)npts * 2 + 1, &R->pts));
-  GH_TRY(ctx->reserve(B_GRID2_START, (size_t)total + 2, &R->start));
+  const GridSlots sl = {B_GRID2_KEYS, B_GRID2_KEYS2, B_GRID2_VALS, B_GRID2_VALS2, B_GRID2_START, B_GRID2_PTS};
+  GridBufs B;
+  GH_TRY(gh_grid_reserve(ctx, sl, (size_t)npts * 2, (size_t)total, true, &B));
+  R->keys = B.keys; R->keys2 = B.keys2; R->vals = B.vals; R->vals2 = B.vals2; R->pts = B.pts; R->start = B.start;
   GH_TRY(ctx->reserve(B_RR_LIDX, (size_t)npts + 1, &R->lidx));
   GH_TRY(ctx->reserve(B_ICP_Q, (size_t)npts + 1, &R->q));
   GH_TRY(ctx->reserve(B_ICP_NN2, (size_t)npts + 1, &R->nn2));
@@ -213,7 +181,7 @@ int gh_refine_recip_step(ghicp_ctx* ctx, const RefineArgs& A, const RecipStage& 
   hipStream_t s = ctx->stream;
   const long long n2 = 2 * R.npts;
   hipEvent_t kg = ctx->kt_begin(KT_REFINE_GRID);
-  hipLaunchKernelGGL(k_rr_box_init, dim3(cdiv(np * 6ll, 256)), dim3(256), 0, s, R.box, np * 6);
+  hipLaunchKernelGGL(k_box_init, dim3(cdiv(np * 6ll, 256)), dim3(256), 0, s, R.box, np * 6);
   hipLaunchKernelGGL(k_rr_box, dim3(min(max_gs, 64), np), dim3(256), 0, s, A, R);
   hipLaunchKernelGGL(k_rr_plan, dim3(cdiv(np, 64)), dim3(64), 0, s, A, R, np);
   hipLaunchKernelGGL(k_rr_keys, dim3(max_gs, np), dim3(256), 0, s, A, R);
